@@ -14,6 +14,11 @@ one 16-byte (cost, index) pair per rank).  The communicator is created at N = 1 
 every bench run.
 `--config 2|3|4` benches the other BASELINE configurations (puzzle_piece, car_seat, trajopt_sqp path) with their own
 roofline object; the default and the headline is config 1.
+A plain run sets up, warms up, times the steps and prints the result line.  `--full` adds what takes time of its own after
+the timed region: the CPU baseline (`cpu_baseline`, skipped with `--no-cpu-baseline`) and the parity of the last timed batch
+against the oracle (`parity`); without it both are null.  `--dump-outputs DIR` writes what the last timed step returned to its
+caller (trajectories, costs, statuses, counters, the best seed and its trajectory) as float64 DIR/<name>.npy; the seeds depend
+on the arguments only, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -43,8 +48,13 @@ def main():
     ap.add_argument("--batch", type=int, default=0, help="seeds per GPU (default: the configuration's BASELINE batch per GPU)")
     ap.add_argument("--depth", type=int, default=None, help="batches in flight (1 = strictly sequential steps, 2 = double-buffered contexts); default 2, and 1 for the HBM-workspace configurations 2 / 3, whose launches are enqueued at once: with two in flight their HIP start event is recorded while the kernel still queues behind the other context, so the launch time would include queue wait and roofline.frac would not be a kernel figure")
     ap.add_argument("--config", type=int, default=1, choices=[1, 2, 3, 4], help="BASELINE.json configuration (default 1 = the metric's)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the parity check")
+    ap.add_argument("--full", action="store_true", help="also run the CPU baseline and the parity check against the oracle")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -112,8 +122,10 @@ def main():
         assert n_active == 0, f"step {k}: {n_active} problems left unfinished by a run-to-completion launch"
         r = c.results()
         best = c.argmin((rank * nsteps + k) * B)   # the only collective: RCCL all-gather of 16 bytes per rank inside the library
+        best_x = None
         if best[0] >= 0:
-            c.best_trajectory()   # ... and its optional last step: the winning T x D trajectory broadcast from its owner rank
+            best_x = c.best_trajectory()[0]   # ... and its optional last step: the winning T x D trajectory broadcast from its owner rank
+        r["best_index"], r["best_cost"], r["best_trajectory"] = best[0], best[1], best_x
         return r, best, c.counters()
 
     for k in range(args.warmup):   # warm-up steps run one at a time
@@ -153,6 +165,18 @@ def main():
         dist.barrier()
     t1 = time.perf_counter()
     elapsed = t1 - t0
+    if args.dump_outputs:
+        # what the last timed step handed its caller, this rank's batch (rank r > 0: <name>_rank<r>.npy); the best seed's index
+        # is global, its trajectory the one broadcast from the owner rank (NaN when no seed of any rank converged)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        suffix = "" if rank == 0 else "_rank%d" % rank
+        bx = last_r["best_trajectory"]
+        outs = {"x": last_r["x"], "total_cost": last_r["total_cost"], "status": last_r["status"],
+                "n_func_evals": last_r["n_func_evals"], "n_qp_solves": last_r["n_qp_solves"],
+                "best_index": np.array([last_r["best_index"]]), "best_cost": np.array([last_r["best_cost"]]),
+                "best_trajectory": bx if bx is not None else np.full((ctx.T, ctx.D), np.nan)}
+        for name, a in outs.items():
+            np.save(os.path.join(args.dump_outputs, name + suffix + ".npy"), np.asarray(a, dtype=np.float64))
     stats = {"admm_ms": 0.0, "convexify_ms": 0.0, "evaluate_ms": 0.0, "admm_launches": 0}
     for c in ctxs:
         st_c = c.kernel_stats()
@@ -236,7 +260,7 @@ def main():
         # (config 4 runs LDS-resident on k_sqp_pool's generic path: like config 1 it is priced against the fp64 roof - it is
         #  bound by dependent-issue latency, not by HBM)
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             from oracle import pyorc
             cores = os.cpu_count() or 1
             pyorc.build()
@@ -295,7 +319,7 @@ def main():
         # 1e-5 rad".  (SQP outcomes are discontinuous in rounding: the seeds outside the ball are the ones on which the oracle parts from
         # its own FMA build as well, tests/test_gpu_parity.py.)
         parity = None
-        if world == 1 and not args.no_cpu_baseline and last_r is not None:
+        if args.full and world == 1 and not args.no_cpu_baseline and last_r is not None:
             from oracle import pyorc
             npar = min(64, B)
             k_last = nsteps - 1

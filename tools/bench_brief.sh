@@ -1,6 +1,6 @@
 #!/bin/bash
 # one-line summary of a bench.py run: value, ms per step, average launch ms, parity block   usage: tools/bench_brief.sh [bench.py args]
-python bench.py "$@" 2>&1 | grep '^{"metric"' | python -c "
+python bench.py --full "$@" 2>&1 | grep '^{"metric"' | python -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 r = d['roofline']

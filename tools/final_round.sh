@@ -5,10 +5,10 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 cd $R
-timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_n1_driver_cmd.log 2> $OUT/bench_n1_driver_cmd.err
-timeout 300 python bench.py > $OUT/bench_n1.log 2> $OUT/bench_n1.err
+timeout 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_n1_driver_cmd.log 2> $OUT/bench_n1_driver_cmd.err
+timeout 300 python bench.py --full > $OUT/bench_n1.log 2> $OUT/bench_n1.err
 bash tools/profile_round.sh $TAG > $OUT/profile.log 2>&1
-for c in 2 3 4; do timeout 300 python bench.py --config $c --steps 2 --warmup 1 > $OUT/bench_cfg$c.log 2>&1; done
+for c in 2 3 4; do timeout 300 python bench.py --full --config $c --steps 2 --warmup 1 > $OUT/bench_cfg$c.log 2>&1; done
 cd /tmp && export TMPDIR=/tmp
 timeout 300 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU_MFMA_MOPS_F64 SQ_INSTS_VALU -d $OUT/pmc_cfg2_mfma -o out --output-format csv -- python $R/bench.py --config 2 --steps 1 --warmup 0 --no-cpu-baseline > $OUT/pmc_cfg2_mfma.json 2> $OUT/pmc_cfg2_mfma.log
 python3 - <<PY

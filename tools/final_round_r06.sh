@@ -25,7 +25,7 @@ python tools/kernel_meta.py trajopt_amd/_build/libtrajopt_mi355x.so k_ > $OUT/ke
 SKIP_KT=1 bash tools/profile_round.sh $TAG > $OUT/profile_pmc.log 2>&1
 cd $R
 [ -f $OUT/pmc_traffic.json ] && cp $OUT/pmc_traffic.json profiles/r06_pmc_traffic.json
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_n1_steps20.log 2> $OUT/bench_n1_steps20.err
+timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_n1_steps20.log 2> $OUT/bench_n1_steps20.err
 grep "^{" $OUT/bench_n1_steps20.log | cut -c1-300
 # kernel trace + stats at the driver's command (summary is rewritten with both parts)
 SKIP_PMC=1 bash tools/profile_round.sh $TAG > $OUT/profile_kt.log 2>&1
@@ -56,7 +56,7 @@ for c in ${CFGS:-2 3 4}; do
   bash tools/profile_cfg.sh $TAG $c > $OUT/profile_cfg$c.log 2>&1
   cd $R
   [ -f $OUT/pmc_traffic_cfg$c.json ] && cp $OUT/pmc_traffic_cfg$c.json profiles/r06_pmc_traffic_cfg$c.json
-  timeout 900 python bench.py --config $c --steps 10 --warmup 2 > $OUT/bench_cfg$c.json 2> $OUT/bench_cfg$c.err
+  timeout 900 python bench.py --full --config $c --steps 10 --warmup 2 > $OUT/bench_cfg$c.json 2> $OUT/bench_cfg$c.err
   grep "^{" $OUT/bench_cfg$c.json | cut -c1-260
 done
 head -30 $OUT/rocprofv3_summary.txt | cut -c1-200

@@ -60,6 +60,7 @@ struct tmx_ctx
   int* h_tail{ nullptr };  // pinned, device-mapped word: 1 once the pool kernel of the pending launch has begun to retire workgroups
   bool dense{ false };      // DevProblem::qp_dense: Model::optimize() by k_qp_solve_dense
   bool band{ false };       // DevProblem::band: the pool driver launches k_sqp_pool_band
+  size_t tt_scratch{ 0 };   // doubles the rank-one terms of TotalTime terms on the block chain add to the per-problem scratch (DevProblem::tt_place 2)
   bool tt_squared{ false }; // a TotalTime cost in its squared form (dense objective block over the time variables)
   bool hull{ false };       // DevProblem::n_ls_hull > 0: the term kernels are the *_hull instantiations (GJK / EPA contacts)
   bool piecewise{ false };  // DevProblem::st: the piecewise driver runs optimize() (host loop) - dense problems and row-only function terms
@@ -80,6 +81,14 @@ struct tmx_ctx
   size_t best_cap{ 0 };
   int max_rec{ 128 };
 };
+
+// size limit of the dense QP engine (QP variables incl. penalty variables); TMX_DENSE_QP_MAX_N lifts it for callers who accept the time
+static int dense_qp_max_n()
+{
+  if (const char* e = std::getenv("TMX_DENSE_QP_MAX_N"))
+    return std::max(1, std::atoi(e));
+  return 448;
+}
 
 template <typename T>
 static tmx_status upload(tmx_ctx* ctx, std::vector<void*>& pool, T** dst, const std::vector<T>& src)
@@ -463,6 +472,8 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
   int n_fx_cost = 0;
   int n_stencil = 0;      // rows of difference order 2 / 3
   bool qp_dense = false;  // time-squared costs, difference rows next to general pair rows: dense QP engine
+  bool tt_terms = false;  // TotalTime terms: dense engine, or - above its size limit - rank-one terms on the block chain
+  bool tt_chain = false;
   bool dyn_p = false;     // function COSTS (CostFromFunc / squared CostFromErrFunc): dynamic D x D objective blocks on the structured solver (round 5)
   bool stencil_rows = false;  // difference rows of order 2 / 3 (JointAcc / JointJerk Ineq costs, Eq / Ineq constraints)
   int max_row_order = 0;
@@ -1268,7 +1279,7 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
           tt_coeff.push_back(tm.coeff);
           tt_limit.push_back(tm.margin);
           st_terms = true;
-          qp_dense = true;
+          tt_terms = true;  // (dense engine or rank-one terms on the block chain: decided below, when every term is known)
           break;
         }
         default:
@@ -1314,6 +1325,21 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
   for (int c = 0; c < P.NX; ++c)
     p_colptr[c + 1] = p_colptr[c] + ((c >= 3 * D && po3[c - 3 * D] != 0.0) ? 1 : 0) + ((c >= 2 * D && po2[c - 2 * D] != 0.0) ? 1 : 0) +
                       ((c >= D && po[c - D] != 0.0) ? 1 : 0) + ((pd[c] != 0.0) ? 1 : 0);
+  // TotalTime terms couple all time variables: one global row (HINGE / EQ / INEQ forms) or a dense objective block 2 c g g' over
+  // tau[1 .. T-1] (SQUARED form).  Small problems keep the dense engine, bit for bit as before.  A problem over the dense engine's
+  // size limit whose ONLY reason for that engine are these terms runs on the block chain instead: the terms become rank-one
+  // corrections of the reduced KKT matrix (QpWs::ttn, tmx_qp.h), at any size.  TMX_TOTAL_TIME_CHAIN: "1" the chain at any size,
+  // "0" never (the dense engine and its limit).  Problems that need the dense engine for another reason as well (squared
+  // velocity-with-time costs, acceleration / jerk rows), banded objectives, function costs and more than TMX_TT_MAX terms stay there.
+  if (tt_terms)
+  {
+    const char* e = std::getenv("TMX_TOTAL_TIME_CHAIN");
+    const bool able = TMX_LINK_ROWS && !qp_dense && !stencil_rows && band == 0 && !dyn_p && (int)tt_owner.size() <= TMX_TT_MAX;
+    const bool want = (e && e[0] == '1') || (!(e && e[0] == '0') && P.n_max > dense_qp_max_n());
+    tt_chain = able && want;
+    if (!tt_chain)
+      qp_dense = true;
+  }
   // Difference ROWS of order 2 / 3 touch one joint each: as long as every row on several waypoints is such a single-joint row (no
   // LVS / cast collision rows, no CartVel rows) all the blocks they add to the reduced KKT matrix are diagonal, and the problem runs
   // on the banded structured path at any size (band = max of the orders of costs and rows; DevProblem::band_rows).  Next to general
@@ -1346,6 +1372,8 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
   P.n_stencil = n_stencil;
   P.qp_dense = qp_dense ? 1 : 0;
   P.st = (qp_dense || st_terms) ? 1 : 0;
+  P.tt_chain = tt_chain ? (int)tt_owner.size() : 0;
+  P.tt_place = 0;
   // convex-hull links: their contact code (GJK / EPA) is instantiated in the piecewise kernels only (template flag HULL)
   {
     int n_hull = 0;
@@ -1700,6 +1728,27 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
     }
   }
 #endif
+  // LDS budgets
+  ctx->smem_qp = qp_smem_bytes(D, T, R, NA, R2, P.coef_far);
+  ctx->tt_scratch = 0;
+  if (P.tt_chain > 0)
+  {
+    // per-problem data of the rank-one terms (g, Z = K_chain^-1 g: read by every ADMM iteration): behind the QP workspace when it
+    // stays in LDS with them, or lives in HBM anyway (long horizons); in the per-problem scratch when they alone would push an
+    // LDS-resident workspace out
+    const size_t tt_bytes = (qp_tt_doubles(D, T, P.tt_chain) + 2) * sizeof(double);
+    const char* force = std::getenv("TMX_TT_PLACE");  // test hook: "2" = in the per-problem scratch whatever the sizes
+    if (TMX_QP_COLD_IN_LDS && !(force && force[0] == '2') && (ctx->smem_qp > 160 * 1024 || ctx->smem_qp + tt_bytes <= 160 * 1024))
+    {
+      P.tt_place = 1;
+      ctx->smem_qp += tt_bytes;
+    }
+    else
+    {
+      P.tt_place = 2;
+      ctx->tt_scratch = tt_bytes / sizeof(double);
+    }
+  }
   if (!ctx->dp)
   {
     void* p = nullptr;
@@ -1707,8 +1756,10 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
     ctx->dp = static_cast<DevProblem*>(p);
   }
   HIPCHK(hipMemcpy(ctx->dp, &P, sizeof(DevProblem), hipMemcpyHostToDevice));
-  // LDS budgets
-  ctx->smem_qp = qp_smem_bytes(D, T, R, NA, R2, P.coef_far);
+  if (std::getenv("TMX_VERBOSE"))
+    std::fprintf(stderr, "[tmx] QP engine: %s; TotalTime terms %d, as rank-one terms on the block chain %d (their data %s)\n",
+                 P.qp_dense ? "dense" : (P.st ? "structured, piecewise driver" : "structured"), P.n_tt, P.tt_chain,
+                 P.tt_place == 1 ? "behind the QP workspace" : (P.tt_place == 2 ? "in the per-problem scratch" : "-"));
   if (std::getenv("TMX_VERBOSE"))
     std::fprintf(stderr, "[tmx] problem: D %d (joints %d), T %d, row slots %d, aux %d, pair rows %d, workspace flags %d, band %d, dense %d, QP workspace %zu B, wave-pair solver %d (LDS %zu B, largest lane group %d, second slack in row slots 0x%x)\n", D, P.DK, T, R, NA, R2,
                  P.coef_far, P.band, (int)P.qp_dense, ctx->smem_qp, P.wave_ok, ctx->smem_wave, P.wv_gmax, P.wv_aux2);
@@ -1728,15 +1779,28 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
     // problem on an HBM-resident matrix: fine for the few-hundred-variable QPs of the reference's KATs, minutes per batch at the
     // size of BASELINE config 1 with smoothing costs (n = 572: a 64-seed batch did not finish in 800 s).  Refuse instead of hanging;
     // TMX_DENSE_QP_MAX_N lifts the limit for callers who accept the time.
-    int max_n = 448;
-    if (const char* e = std::getenv("TMX_DENSE_QP_MAX_N"))
-      max_n = std::max(1, std::atoi(e));
-    if (P.n_max > max_n)
+    if (P.n_max > dense_qp_max_n())
     {
-      ctx->err = "squared time-parameterised costs (or acceleration / jerk rows next to collision / CartVel rows on two waypoints): the QP of "
-                 "this problem has too many variables for the dense engine to solve in practical time (limit 448 incl. penalty variables; "
-                 "TMX_DENSE_QP_MAX_N overrides); function costs, smoothing costs, acceleration / jerk limits and function terms that are rows "
-                 "(constraints, ABS / HINGE costs, AvoidSingularity, DynamicCartPose) have no such limit";
+      // what put the problem on the dense engine (TotalTime terms alone do not at this size: they run on the block chain unless one
+      // of the reasons below keeps them off it)
+      std::string why;
+      auto reason = [&why](const std::string& r) { why += (why.empty() ? "" : ", ") + r; };
+      if (P.n_tv > 0)
+        reason("squared joint-velocity costs with time");
+      if (stencil_rows)
+        reason("acceleration / jerk rows next to collision / CartVel rows on two waypoints or to time-parameterised terms");
+      if (tt_terms && (int)tt_owner.size() > TMX_TT_MAX)
+        reason("more than " + std::to_string(TMX_TT_MAX) + " TotalTime terms");
+      else if (tt_terms && (band != 0 || dyn_p))
+        reason("TotalTime terms next to acceleration / jerk costs or function costs");
+      else if (tt_terms && P.n_tv == 0 && !stencil_rows)
+        reason("TotalTime terms with TMX_TOTAL_TIME_CHAIN=0 (or a build without rows on two waypoints)");
+      if (why.empty())
+        reason("acceleration / jerk costs next to rows on two waypoints or function costs");
+      ctx->err = why + ": the QP of this problem has too many variables for the dense engine to solve in practical time (limit 448 incl. "
+                 "penalty variables; TMX_DENSE_QP_MAX_N overrides); TotalTime terms alone (up to " + std::to_string(TMX_TT_MAX) + "), function costs, "
+                 "smoothing costs, acceleration / jerk limits and function terms that are rows (constraints, ABS / HINGE costs, AvoidSingularity, "
+                 "DynamicCartPose) have no such limit";
       ctx->have_problem = false;
       return TMX_ERR_UNSUPPORTED;
     }
@@ -1957,6 +2021,8 @@ static tmx_status ensure_batch(tmx_ctx* ctx, int B)
     AL(tt_aff, b * (size_t)P.n_tt * (P.T + 1));
   H.tail_flag = ctx->h_tail;  // pinned host memory is device-accessible at the same address (unified addressing)
   H.qp_scratch_stride = (long long)qp_scratch_doubles(P.D, P.T, P.R, P.NA, P.n_link, P.coef_far);
+  if (ctx->tt_scratch > 0)  // rank-one terms of TotalTime terms behind everything else (qp_ws_attach_tt)
+    H.qp_scratch_stride = (long long)(((qp_scratch_doubles(P.D, P.T, P.R, P.NA, P.n_link, P.coef_far) + 1) & ~(size_t)1) + ctx->tt_scratch);
   if (P.wave_ok)  // the one-wave solver keeps the cold part of the workspace behind the far part (wave_ws_carve)
     H.qp_scratch_stride = (long long)(((qp_far_doubles(P.D, P.T, P.R, P.NA, 0, P.coef_far) + 1) & ~(size_t)1) + qp_glb_doubles(P.D, P.T, P.R, P.NA, 0, P.coef_far) + 8);
   AL(qp_scratch, b * (size_t)H.qp_scratch_stride);

@@ -262,11 +262,22 @@ struct QpWs
   // its first NX doubles serve band_solve as the intermediate vector)
   double *po2, *po3, *Wb, *Mb;
   int band;
+  int ttn;  // (see RANK-ONE TERMS below)
   // DYNAMIC OBJECTIVE BLOCKS (round 5): the off-diagonal entries of the D x D diagonal blocks of P of a problem with function costs
   // (sco::CostFromFunc / squared CostFromErrFunc models of one waypoint, modeling_utils.cpp:52-113): pb[t D D + i D + j], symmetric,
   // zero diagonal (the diagonal entries are part of pd).  nullptr everywhere else - a literal in every instantiation but the piecewise
   // QP kernels (qp_solve_block<., ., ROWSK = true>), so the pool / fused kernels and the out-of-line loops carry none of this code.
   double* pb;
+  // RANK-ONE TERMS OVER THE TIME VARIABLES (TotalTime terms on the block chain, DevProblem::tt_chain): term k is a vector g_k over
+  // tau[1 .. T-1] (ws_ttg(w)[k T + t], scaled like the matrix entries it stands for; entry 0 and an inactive row's entries are 0.0)
+  // that is either the GLOBAL ROW ws_ttr(w)[k] of A (forms HINGE / EQ / INEQ: the row's D home coefficients are zero, all it has is
+  // g_k) or, with ws_ttr(w)[k] = -1, the objective block ttw[k] g_k g_k' of P (SQUARED form, ttw = 2 coeff).  The reduced KKT matrix
+  // is K_chain + U W U' (U = the g_k as columns over all primary variables, W = diag of the rows' effective weights / of ttw):
+  // tt_factor keeps Z = K_chain^-1 U (ws_ttz(w)[k NX + v]) and ttm = (I + W U'Z)^-1 W (k x k, row major), tt_correct applies
+  // x = y - Z ttm (U'y) behind every chain solve.  ttn (number of terms) and tto (where their data are: > 0 doubles behind xp,
+  // < 0 behind Da - qp_ws_attach_tt) sit in two alignment holes of this descriptor: its size, and with it the stack frames and the
+  // LDS layout of every kernel, are what they were.  ttn is the literal 0 of qp_ws_carve everywhere but in the piecewise QP kernels
+  // (qp_solve_block<., ., ROWSK = true>), like pb == nullptr.
   // DIFFERENCE ROWS of order 2 / 3 on the banded structured path (DevProblem::band_rows: JointAcc / JointJerk Ineq costs and
   // constraints, trajectory_costs.cpp:556-754, :811-1016): such a row touches ONE joint j on waypoints t .. t + order.  coef / c2
   // hold its entries on t and t + 1 (D-vectors that are zero off joint j), cf[2 i], cf[2 i + 1] (i = the row's c2 index) the
@@ -288,6 +299,7 @@ struct QpWs
   // sub-matrices (P slots of Gn rows, row stride Gs) and of the separator Schur complement (ns rows, stride Zst)
   double *G, *Zs;
   int Gn, Gs, Zst;
+  int tto;  // (see RANK-ONE TERMS above)
   double *sx;  // 6*64: separator exchange: [0) c*y of the interior left of each separator, [64) right, [128) c*x_sep
                // towards the left interior, [192) towards the right one, [256) Gauss-Jordan column scratch
   double *ty;  // P*Gs + 64: right-hand side of the dense solve, permuted (interior k at k*Gs, separators after)
@@ -343,6 +355,82 @@ TMX_DEVFN double* ws_dd(const QpWs& w)  // (even offset: 16-byte aligned pairs)
 }
 // the chains of problems WITHOUT pair rows couple consecutive blocks through the diagonal of the objective only
 #define TMX_PC(w) ((w).po)
+// ---- rank-one terms over the time variables (QpWs::ttn) ---------------------------------------------------------------------
+#define TMX_TT_MAX 4  // terms per problem on the block chain (more keep the dense engine: tmx_problem_upload)
+TMX_HOSTDEVFN size_t qp_tt_doubles(int D, int T, int K)
+{
+  return K > 0 ? (size_t)K * ((size_t)T + (size_t)D * T) + (size_t)K * K + 2 * (size_t)K + 4 : 0;
+}
+// layout: g (K T, padded to even) | Z (K NX, padded) | ttm (K K) | ttw (K) | row slots (K ints)
+TMX_DEVFN double* ws_ttg(const QpWs& w) { return w.tto > 0 ? w.xp + w.tto : w.Da - w.tto; }
+TMX_DEVFN double* ws_ttz(const QpWs& w) { return ws_ttg(w) + (((size_t)w.ttn * w.T + 1) & ~(size_t)1); }
+TMX_DEVFN double* ws_ttm(const QpWs& w) { return ws_ttz(w) + (((size_t)w.ttn * w.NX + 1) & ~(size_t)1); }
+TMX_DEVFN double* ws_ttw(const QpWs& w) { return ws_ttm(w) + w.ttn * w.ttn; }
+TMX_DEVFN int* ws_ttr(const QpWs& w) { return reinterpret_cast<int*>(ws_ttw(w) + w.ttn); }
+// g_k . x over tau[1 .. T-1].  ONE thread forms the whole sum, as four interleaved partial sums in a fixed order: the result does
+// not depend on the number of threads of the workgroup (host build: 1, device: 256 / 512), and a thread that needs the value
+// computes it instead of waiting for a reduction - T - 1 terms against the 2 (T - 1) dependent block steps of the chain solve.
+TMX_DEVFN double tt_dot(const QpWs& w, int k, const double* x)
+{
+  const int D = w.D, T = w.T;
+  const double* g = ws_ttg(w) + (size_t)k * T;
+  double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+  int t = 1;
+  for (; t + 3 < T; t += 4)
+  {
+    s0 += g[t] * x[t * D + D - 1];
+    s1 += g[t + 1] * x[(t + 1) * D + D - 1];
+    s2 += g[t + 2] * x[(t + 2) * D + D - 1];
+    s3 += g[t + 3] * x[(t + 3) * D + D - 1];
+  }
+  for (; t < T; ++t)
+    s0 += g[t] * x[t * D + D - 1];
+  return (s0 + s1) + (s2 + s3);
+}
+// (A x)_r part of a global row r (0.0 for every other row)
+TMX_DEVFN double tt_row_dot(const QpWs& w, int r, const double* x)
+{
+  double s = 0.0;
+  for (int k = 0; k < w.ttn; ++k)
+    if (ws_ttr(w)[k] == r)
+      s += tt_dot(w, k, x);
+  return s;
+}
+// (A'rv) contribution of the global rows to variable (t, j)
+TMX_DEVFN double tt_gather(const QpWs& w, const double* rv, int t, int j)
+{
+  double s = 0.0;
+  if (j == w.D - 1)
+    for (int k = 0; k < w.ttn; ++k)
+      if (ws_ttr(w)[k] >= 0)
+        s += rv[ws_ttr(w)[k]] * ws_ttg(w)[(size_t)k * w.T + t];
+  return s;
+}
+// (P x)_v part of the squared forms
+TMX_DEVFN double tt_p_times(const QpWs& w, const double* x, int v)
+{
+  double s = 0.0;
+  if (v % w.D == w.D - 1)
+    for (int k = 0; k < w.ttn; ++k)
+      if (ws_ttr(w)[k] < 0)
+        s += (ws_ttw(w)[k] * ws_ttg(w)[(size_t)k * w.T + v / w.D]) * tt_dot(w, k, x);
+  return s;
+}
+// largest |entry| of column (t, D - 1) of P that the squared forms add: |ttw g_t g_s| over s
+TMX_DEVFN double tt_p_col_norm(const QpWs& w, int t)
+{
+  double cn = 0.0;
+  for (int k = 0; k < w.ttn; ++k)
+    if (ws_ttr(w)[k] < 0)
+    {
+      const double* g = ws_ttg(w) + (size_t)k * w.T;
+      double gm = 0.0;
+      for (int s = 1; s < w.T; ++s)
+        gm = fmax(gm, fabs(g[s]));
+      cn = fmax(cn, fabs((ws_ttw(w)[k] * g[t]) * gm));
+    }
+  return cn;
+}
 #if TMX_LINK_ROWS
 #define TMX_HAS_PAIRS(w) ((w).n_link > 0)
 // x-part of row r (home waypoint t) on the next waypoint
@@ -350,7 +438,7 @@ TMX_DEVFN double link_dot(const QpWs& w, int r, int t, const double* x)
 {
   const int i = w.c2i[r];
   if (i < 0)
-    return 0.0;
+    return w.ttn > 0 ? tt_row_dot(w, r, x) : 0.0;  // (a global row has no second block)
   double s = 0.0;
   for (int j = 0; j < w.D; ++j)
     s += w.c2[i * w.D + j] * x[(t + 1) * w.D + j];
@@ -428,6 +516,8 @@ TMX_DEVFN double link_gather(const QpWs& w, const double* rv, int t, int j)
   }
   if (w.band_rows)
     s += far_gather(w, rv, t, j);
+  if (w.ttn > 0)
+    s += tt_gather(w, rv, t, j);
   return s;
 }
 #else
@@ -648,6 +738,8 @@ TMX_DEVFN void qp_ws_carve(QpWs& w, double* lds, double* glb, double* far, int D
   w.band = 0;
   w.po2 = w.po3 = w.Wb = w.Mb = nullptr;
   w.pb = nullptr;
+  w.ttn = 0;
+  w.tto = 0;
   w.bk = nullptr;
   w.band_rows = 0;
   w.polish_dd = 0;
@@ -810,6 +902,18 @@ TMX_DEVFN void qp_ws_carve(QpWs& w, double* lds, double* glb, double* far, int D
   }
 #undef TAKE
 #undef TAKEI
+}
+
+// Storage of the rank-one terms over the time variables (DevProblem::tt_chain terms): behind the QP workspace `ws` (LDS, or the
+// HBM slice of a long-horizon problem - tt_place 1) or behind everything else of the per-problem scratch (tt_place 2: the
+// workspace fills the LDS without them)
+TMX_DEVFN void qp_ws_attach_tt(QpWs& w, const DevProblem* P, double* ws, double* scratch)
+{
+  const int K = P->tt_chain, D = P->D, T = P->T;
+  double* p = (P->tt_place == 1) ? ws + ((qp_smem_bytes(D, T, P->R, P->NA, P->n_link, P->coef_far) / sizeof(double) + 1) & ~(size_t)1)
+                                 : scratch + ((qp_scratch_doubles(D, T, P->R, P->NA, P->n_link, P->coef_far) + 1) & ~(size_t)1);
+  w.ttn = K;
+  w.tto = (P->tt_place == 1) ? (int)(p - w.xp) : -(int)(p - w.Da);  // (xp: first array of the cold part; Da: in the scratch, and not one of the arrays the polish re-points)
 }
 
 // row sweep over the slots the workspace says exist: `for r in rows` visits all R slots, or only the active rows when the
@@ -2087,6 +2191,43 @@ TMX_DEVFN void chain_diag_sweep_d(MP Sinv, CP cpl, VP tp, int D, int DS, int DDS
 #else
 #define TMX_FTICK(f, slot) ((void)0)
 #endif
+// Low-rank correction behind a chain solve: w.tp holds y = K_chain^-1 b (all threads past the barrier that ends the chain solve) and
+// leaves with x = y - Z ttm (U'y), the solution of (K_chain + U W U') x = b.  Every thread forms the ttn dot products itself
+// (tt_dot: fixed order, broadcast reads of the time entries of y), so the correction costs no reduction: one barrier before the
+// time entries are overwritten, one axpy over the primary variables, one barrier behind it.
+TMX_DEVFN void tt_correct(const QpWs& w, int tid, int NT)
+{
+  const int K = w.ttn, NX = w.NX;
+  double c[TMX_TT_MAX];
+  {
+    double u[TMX_TT_MAX];
+#pragma unroll
+    for (int k = 0; k < TMX_TT_MAX; ++k)
+      u[k] = (k < K) ? tt_dot(w, k, w.tp) : 0.0;
+#pragma unroll
+    for (int k = 0; k < TMX_TT_MAX; ++k)
+    {
+      double a = 0.0;
+#pragma unroll
+      for (int l = 0; l < TMX_TT_MAX; ++l)
+        if (k < K && l < K)
+          a += ws_ttm(w)[k * K + l] * u[l];
+      c[k] = a;
+    }
+  }
+  TMX_SYNC();
+  for (int v = tid; v < NX; v += NT)
+  {
+    double a = 0.0;
+#pragma unroll
+    for (int k = 0; k < TMX_TT_MAX; ++k)
+      if (k < K)
+        a += ws_ttz(w)[(size_t)k * NX + v] * c[k];
+    w.tp[v] -= a;
+  }
+  TMX_SYNC();
+}
+
 TMX_DEVFN void kkt_solve(const QpWs& w, const DevProblem* P, int mode, double sig, double delta, int tid, int NT,
                          [[maybe_unused]] long long* fpc = nullptr, [[maybe_unused]] long long* ftl = nullptr)
 {
@@ -2311,6 +2452,8 @@ TMX_DEVFN void kkt_solve(const QpWs& w, const DevProblem* P, int mode, double si
     std::printf("[dbg] reduced solve: |K x - b| %.3e  |b| %.3e  polish_dd %d\n", rmax, bmax, w.polish_dd);
   }
 #endif
+  if (w.ttn > 0)
+    tt_correct(w, tid, NT);  // rank-one terms over the time variables
   // 3. aux recovery and (A x)_r   (polish: hr = nu_r, the multiplier itself - (A dx - r2) / delta would cancel again)
   if (mode == 1)
   {
@@ -2506,6 +2649,8 @@ TMX_DEVFN double p_times(const QpWs& w, const double* x, int v)
     s += w.po[v - D] * x[v - D];
   if (t < w.T - 1)
     s += w.po[v] * x[v + D];
+  if (w.ttn > 0)
+    s += tt_p_times(w, x, v);
   if (w.band)
   {
     // (exprToEigen's column order is irrelevant for a product; the far couplings follow the near ones)
@@ -3301,6 +3446,56 @@ TMX_DEVFN void chain_solve(const QpWs& w, int tid, int NT)
   }
 #endif
   chain_solve_range(w, 0, w.T - 1, tid, NT);
+}
+
+// Factor stage of the rank-one terms: call behind kkt_factor + kkt_invert (w.hr = the rows' effective weights of kkt_factor, the
+// chain inverted; w.tp is free).  Z = K_chain^-1 U by ttn chain solves, then ttm = (I + W U'Z)^-1 W by Gauss-Jordan on the ttn x ttn
+// system (thread 0; K_chain and W U'Z W are positive (semi)definite, no pivoting needed).  Written with W as a factor instead of
+// W^-1 + U'Z: a term of weight zero - an inactive row, a row outside the polish's active set - has a zero row in ttm and
+// drops out of the correction, nothing is divided by it.
+TMX_DEVFN void tt_factor(const QpWs& w, int tid, int NT)
+{
+  const int K = w.ttn, NX = w.NX, T = w.T, D = w.D;
+  for (int k = 0; k < K; ++k)
+  {
+    for (int v = tid; v < NX; v += NT)
+      w.tp[v] = (v % D == D - 1) ? ws_ttg(w)[(size_t)k * T + v / D] : 0.0;
+    TMX_SYNC();
+    chain_solve(w, tid, NT);
+    for (int v = tid; v < NX; v += NT)
+      ws_ttz(w)[(size_t)k * NX + v] = w.tp[v];
+    TMX_SYNC();
+  }
+  if (tid == 0)
+  {
+    double M[TMX_TT_MAX][2 * TMX_TT_MAX];
+    for (int k = 0; k < K; ++k)
+    {
+      const double wk = (ws_ttr(w)[k] >= 0) ? w.hr[ws_ttr(w)[k]] : ws_ttw(w)[k];
+      for (int l = 0; l < K; ++l)
+      {
+        M[k][l] = ((k == l) ? 1.0 : 0.0) + wk * tt_dot(w, k, ws_ttz(w) + (size_t)l * NX);
+        M[k][K + l] = (k == l) ? wk : 0.0;
+      }
+    }
+    for (int c = 0; c < K; ++c)
+    {
+      const double piv = 1.0 / M[c][c];
+      for (int l = 0; l < 2 * K; ++l)
+        M[c][l] *= piv;
+      for (int k = 0; k < K; ++k)
+        if (k != c)
+        {
+          const double f = M[k][c];
+          for (int l = 0; l < 2 * K; ++l)
+            M[k][l] -= f * M[c][l];
+        }
+    }
+    for (int k = 0; k < K; ++k)
+      for (int l = 0; l < K; ++l)
+        ws_ttm(w)[k * K + l] = M[k][K + l];
+  }
+  TMX_SYNC();
 }
 
 // Phase C: aux recovery, ztilde, and the x / z / y updates (rows + their aux, primary vars)

@@ -1229,6 +1229,8 @@ TMX_DEVFN void qp_admm_generic_loop(QpWs& w, const DevProblem* P, QpInfo& info, 
       admm_phase_b(w, P, tid, NT);
       TMX_TICK(3);
       chain_solve(w, tid, NT);
+      if (w.ttn > 0)
+        tt_correct(w, tid, NT);  // rank-one terms over the time variables (piecewise QP kernels only)
       TMX_TICK(4);
       admm_phase_c(w, can_check || do_rho, tid, NT);
       TMX_TICK(5);
@@ -1258,6 +1260,8 @@ TMX_DEVFN void qp_admm_generic_loop(QpWs& w, const DevProblem* P, QpInfo& info, 
         TMX_TICK(6);
         kkt_factor(w, P, 0, w.sigma, st.delta, tid, NT);
         kkt_invert(w, false, tid, NT, pc, tlast);
+        if (w.ttn > 0)
+          tt_factor(w, tid, NT);
         admm_cache_weights(w, tid, NT);
         TMX_TICK(15);
       }
@@ -1281,13 +1285,15 @@ TMX_DEVFN void qp_admm_generic_loop(QpWs& w, const DevProblem* P, QpInfo& info, 
 // one load + wait per term - with the additions in the same order (results bit-identical).
 // BAND = true: the instantiation for banded objectives (acceleration / jerk costs; never with pair rows).  Every other
 // instantiation keeps the literal band = 0 of qp_ws_carve: no banded code, no calls in the loops of configs 1 - 4.
+// TT = true: the instantiations for TotalTime terms on the block chain (DevProblem::tt_chain; piecewise QP kernels only): every
+// other one keeps the literal ttn = 0 of qp_ws_carve and none of the rank-one correction.
 #ifndef TMX_D10_INSTANTIATION
 #define TMX_D10_INSTANTIATION 1  // block-size-10 instantiation of the pair-row loop for config 3 (10-DOF arm + positioner, HBM workspace): +21.6 %,
                                  // bit-identical (profiles/r05/r05j_ab_d10_instantiation_cfg3.log).  Rounds 3 - 4 recorded it as "faulted in the
                                  // 512-thread HBM kernel - memory access fault at address 0, not understood": the stale register of round 5's
                                  // END_CF finding (trajopt_amd/csrc/Makefile)
 #endif
-template <bool HBM, bool PAIRS, int DC, bool BAND = false>
+template <bool HBM, bool PAIRS, int DC, bool BAND = false, bool TT = false>
 __device__ __attribute__((noinline)) static void qp_admm_generic_nl(const DevProblem* P_in, const DevBatch* Bt_in, int b_in, unsigned lds_in,
                                                                   double* work_in, int chain_in_lds)
 {
@@ -1309,6 +1315,8 @@ __device__ __attribute__((noinline)) static void qp_admm_generic_nl(const DevPro
 #endif
     if (HBM && __builtin_amdgcn_readfirstlane(chain_in_lds) != 0)
       qp_ws_chain_to_lds(w, lds);
+    if constexpr (TT)
+      qp_ws_attach_tt(w, P, smem, scratch);
   }
 #if TMX_LINK_ROWS
   w.c2i = P->slot_c2;
@@ -1389,6 +1397,10 @@ TMX_DEVFN void qp_solve_block(const DevProblem* P, const DevBatch* Bt, int b, do
       dyn_H = Bt->fx_H + (size_t)b * P->n_fx_cost * D * D;
       dyn_g = Bt->fx_g + (size_t)b * P->n_fx_cost * D;
     }
+  // TotalTime terms on the block chain (piecewise kernels only): rank-one terms over the time variables
+  if constexpr (ROWSK)
+    if (P->tt_chain > 0)
+      qp_ws_attach_tt(w, P, smem, Bt->qp_scratch + (size_t)b * Bt->qp_scratch_stride);
   long long pc[16] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
   long long tlast = TMX_CLK();
   const int* g_act = Bt->active + (size_t)b * R;
@@ -1481,6 +1493,35 @@ TMX_DEVFN void qp_solve_block(const DevProblem* P, const DevBatch* Bt, int b, do
             qv += dyn_g[(size_t)P->fx_ci[c] * D + v % D];
           }
         w.pd[v] = P->pd[v] + dv;
+        w.qp[v] = qv;
+      }
+    if constexpr (ROWSK)
+      if (w.ttn > 0 && j == D - 1)
+      {
+        // the terms' entries on tau[t] (t = v / D): the global row's coefficient (tt_row_entry; 0.0 while the row is inactive) or, for
+        // the squared form (exprSquare of the affine model: P += 2 coeff g g', q += 2 coeff k g), the gradient itself
+        const int t = v / D;
+        const double* aff = Bt->tt_aff + (size_t)b * P->n_tt * (T + 1);
+        double qv = w.qp[v];
+        for (int k = 0; k < w.ttn; ++k)
+        {
+          double gv = 0.0;
+          if (t >= 1 && P->tt_form[k] == 0)
+          {
+            gv = aff[(size_t)k * (T + 1) + t];
+            const double lin = ((2 * aff[(size_t)k * (T + 1) + T]) * gv) * P->tt_coeff[k];
+            if (lin != 0.0)
+              qv += lin;
+          }
+          else if (t >= 1 && P->tt_slot[k] >= 0 && g_act[P->tt_slot[k]])
+            gv = tt_row_entry(P, aff, k, t);
+          ws_ttg(w)[(size_t)k * T + t] = gv;
+          if (t == 1)
+          {
+            ws_ttw(w)[k] = (P->tt_form[k] == 0) ? 2.0 * P->tt_coeff[k] : 0.0;
+            ws_ttr(w)[k] = P->tt_slot[k];
+          }
+        }
         w.qp[v] = qv;
       }
     w.po[v] = (v < NX - D) ? P->po[v] : 0.0;
@@ -1644,6 +1685,14 @@ TMX_DEVFN void qp_solve_block(const DevProblem* P, const DevBatch* Bt, int b, do
               cn = fmax(cn, fabs(ws_cf(w)[2 * ci + (k - 2)]));
           }
 #endif
+      if (w.ttn > 0 && j == D - 1)
+      {
+        // rank-one terms over the time variables: the global rows' entries in this column, the squared forms' column of P
+        for (int k = 0; k < w.ttn; ++k)
+          if (ws_ttr(w)[k] >= 0)
+            cn = fmax(cn, fabs(ws_ttg(w)[(size_t)k * T + t]));
+        cn = fmax(cn, tt_p_col_norm(w, t));
+      }
       cn = fmax(cn, fabs(w.bbp[v]));
       w.tp[v] = 1.0 / sqrt(limit_scaling(cn));
       t_ebp[v] = 1.0 / sqrt(limit_scaling(fabs(w.bbp[v])));
@@ -1662,6 +1711,10 @@ TMX_DEVFN void qp_solve_block(const DevProblem* P, const DevBatch* Bt, int b, do
       if (w.band_rows && w.c2i[r] >= 0 && ws_fo(w)[w.c2i[r]] != 0)
         rn = fmax(rn, fmax(fabs(ws_cf(w)[2 * w.c2i[r]]), fabs(ws_cf(w)[2 * w.c2i[r] + 1])));
 #endif
+      for (int k = 0; k < w.ttn; ++k)
+        if (ws_ttr(w)[k] == r)  // global row: its entries on the time variables
+          for (int t = 1; t < T; ++t)
+            rn = fmax(rn, fabs(ws_ttg(w)[(size_t)k * T + t]));
       for (int k = 0; k < w.naux[r]; ++k)
       {
         const int a = w.aoff[r] + k;
@@ -1688,6 +1741,15 @@ TMX_DEVFN void qp_solve_block(const DevProblem* P, const DevBatch* Bt, int b, do
       w.qp[v] *= w.tp[v];
       w.Dp[v] *= w.tp[v];
       w.Ebp[v] *= t_ebp[v];
+      if (w.ttn > 0 && v % D == D - 1)
+        for (int k = 0; k < w.ttn; ++k)
+        {
+          double& gv = ws_ttg(w)[(size_t)k * T + v / D];
+          if (ws_ttr(w)[k] < 0)
+            gv *= w.tp[v];  // (squared form: P_ts = ttw g_t g_s, scaled on both sides)
+          else if (w.act[ws_ttr(w)[k]])
+            gv = (w.hr[ws_ttr(w)[k]] * gv) * w.tp[v];
+        }
     }
     if (w.pb != nullptr)
       for (int e = tid; e < T * D * D; e += NT)
@@ -1741,6 +1803,8 @@ TMX_DEVFN void qp_solve_block(const DevProblem* P, const DevBatch* Bt, int b, do
       if (w.pb != nullptr)
         for (int i = 0; i < D; ++i)
           cn = fmax(cn, fabs(w.pb[(size_t)t * D * D + i * D + v % D]));
+      if (w.ttn > 0 && v % D == D - 1)
+        cn = fmax(cn, tt_p_col_norm(w, t));
       w.tp[v] = cn;
       qmax = fmax(qmax, fabs(w.qp[v]));
     }
@@ -1788,6 +1852,9 @@ TMX_DEVFN void qp_solve_block(const DevProblem* P, const DevBatch* Bt, int b, do
     if (w.pb != nullptr)
       for (int e = tid; e < T * D * D; e += NT)
         w.pb[e] *= ct;
+    if (w.ttn > 0 && tid == 0)
+      for (int k = 0; k < w.ttn; ++k)
+        ws_ttw(w)[k] *= ct;
     TMX_ROWS(w, r)
       if (w.act[r])
         for (int k = 0; k < w.naux[r]; ++k)
@@ -1891,7 +1958,7 @@ TMX_DEVFN void qp_solve_block(const DevProblem* P, const DevBatch* Bt, int b, do
   // ---------------- factor + ADMM loop (osqp_solve) --------------------------------------------------------
   TMX_TICK(0);
 #if TMX_IS_DEVICE
-  const bool fast = TMX_UNI_B(!HBM && (NT == TMX_QP_NT) && (R <= 512) && dpart_supported(w, NT) && !TMX_HAS_PAIRS(w) && w.c_alist == nullptr && w.band == 0 && w.pb == nullptr && TMX_FAST_ALLOWED);
+  const bool fast = TMX_UNI_B(!HBM && (NT == TMX_QP_NT) && (R <= 512) && dpart_supported(w, NT) && !TMX_HAS_PAIRS(w) && w.c_alist == nullptr && w.band == 0 && w.pb == nullptr && w.ttn == 0 && TMX_FAST_ALLOWED);
 #else
   const bool fast = false;
 #endif
@@ -1901,6 +1968,8 @@ TMX_DEVFN void qp_solve_block(const DevProblem* P, const DevBatch* Bt, int b, do
 #endif
   kkt_factor(w, P, 0, w.sigma, st.delta, tid, NT);
   kkt_invert(w, fast, tid, NT, pc, tlast);
+  if (w.ttn > 0)
+    tt_factor(w, tid, NT);
   admm_cache_weights(w, tid, NT);
   TMX_TICK(15);
   QpInfo info;
@@ -1981,7 +2050,14 @@ TMX_DEVFN void qp_solve_block(const DevProblem* P, const DevBatch* Bt, int b, do
     {
       // instantiations: with / without pair rows; block size 7 (7-DOF arms: configs 2 and 4) and, for the HBM-workspace pair-row
       // problems, 10 (config 3) as compile-time constants
-      if (ROWSK && BANDK && P->band && P->n_link > 0)  // banded path with difference rows of order 2 / 3 (DevProblem::band_rows)
+      if (ROWSK && w.ttn > 0)  // TotalTime terms on the block chain (never with a banded objective: tmx_problem_upload)
+      {
+        if (P->n_link > 0)
+          qp_admm_generic_nl<HBM, true, 0, false, true>(P, Bt, b, lds_off, HBM ? smem : nullptr, chain_lds != nullptr ? 1 : 0);
+        else
+          qp_admm_generic_nl<HBM, false, 0, false, true>(P, Bt, b, lds_off, HBM ? smem : nullptr, chain_lds != nullptr ? 1 : 0);
+      }
+      else if (ROWSK && BANDK && P->band && P->n_link > 0)  // banded path with difference rows of order 2 / 3 (DevProblem::band_rows)
         qp_admm_generic_nl<HBM, true, 0, true>(P, Bt, b, lds_off, HBM ? smem : nullptr, chain_lds != nullptr ? 1 : 0);
       else if (P->n_link > 0)
       {
@@ -2124,6 +2200,8 @@ TMX_DEVFN void qp_solve_block(const DevProblem* P, const DevBatch* Bt, int b, do
     TMX_TICK(13);
 #endif
     kkt_invert(wp, false, tid, NT, pc, tlast);
+    if (wp.ttn > 0)
+      tt_factor(wp, tid, NT);
 #ifdef TMX_POLISH_SPLIT
     TMX_TICK(14);
 #endif

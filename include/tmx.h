@@ -325,7 +325,10 @@ typedef struct
      t (n_dof + 1) + j), fixed_steps pin the joint columns only (:485-508), the trust box covers the time column like any other
      variable.  A TMX_TERM_JOINT_VEL_TIME / TMX_TERM_TOTAL_TIME term needs it (:447-448); the converse check of the reference
      (:451-452) is on TermInfo flags and is made by the front ends.  Problems whose time terms are ROWS only (velocity limits, hinge
-     costs) stay on the structured solvers; a squared velocity cost with time selects the dense QP engine (<= 448 QP variables).
+     costs) stay on the structured solvers.  A squared velocity cost with time keeps the dense QP engine up to its size limit (448 QP
+     variables) and runs on the structured solvers above it, on the block chain with dense coupling blocks
+     (TMX_VEL_TIME_CHAIN = 1 / 0: always / never) - alone, next to rows on two waypoints and to other row terms; next to TotalTime
+     terms, acceleration / jerk terms or function costs it stays on the dense engine and is refused above the limit.
      TotalTime terms (up to 4) keep that engine below its size limit and run on the structured solvers above it, as rank-one
      corrections of the block chain (TMX_TOTAL_TIME_CHAIN = 1 / 0: always / never).  n_dof stays the number of JOINTS.          */
   int32_t use_time;

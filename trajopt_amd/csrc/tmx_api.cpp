@@ -474,6 +474,9 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
   bool qp_dense = false;  // time-squared costs, difference rows next to general pair rows: dense QP engine
   bool tt_terms = false;  // TotalTime terms: dense engine, or - above its size limit - rank-one terms on the block chain
   bool tt_chain = false;
+  bool tv_terms = false;  // squared JointVel-with-time costs: dense engine, or - above its size limit - joint - time entries on the dense-coupling block chain
+  bool tv_chain = false;
+  std::string tv_why;     // what keeps such costs on the dense engine (text of the refusal above its size limit)
   bool dyn_p = false;     // function COSTS (CostFromFunc / squared CostFromErrFunc): dynamic D x D objective blocks on the structured solver (round 5)
   bool stencil_rows = false;  // difference rows of order 2 / 3 (JointAcc / JointJerk Ineq costs, Eq / Ineq constraints)
   int max_row_order = 0;
@@ -1230,7 +1233,7 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
                 tv_target.push_back(tm.targets[j]);
                 tv_up.push_back(tm.upper_tols[j]);
                 tv_lo.push_back(tm.lower_tols[j]);
-                qp_dense = true;  // P changes with the iterate and couples a joint with the NEXT waypoint's time variable
+                tv_terms = true;  // P changes with the iterate and couples a joint with the NEXT waypoint's time variable (engine: decided below)
               }
               continue;
             }
@@ -1334,11 +1337,44 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
   if (tt_terms)
   {
     const char* e = std::getenv("TMX_TOTAL_TIME_CHAIN");
-    const bool able = TMX_LINK_ROWS && !qp_dense && !stencil_rows && band == 0 && !dyn_p && (int)tt_owner.size() <= TMX_TT_MAX;
+    const bool able = TMX_LINK_ROWS && !qp_dense && !tv_terms && !stencil_rows && band == 0 && !dyn_p && (int)tt_owner.size() <= TMX_TT_MAX;
     const bool want = (e && e[0] == '1') || (!(e && e[0] == '0') && P.n_max > dense_qp_max_n());
     tt_chain = able && want;
     if (!tt_chain)
       qp_dense = true;
+  }
+  // Squared JointVel-with-time costs (exprSquare of a x[t][j] + b x[t+1][j] + c tau[t+1] + k) put entries that change with the iterate
+  // on (x[t][j], x[t+1][j]), inside block t+1 on (j, tau) and (tau, tau), and between the blocks on (x[t][j], tau[t+1]): P stays block
+  // tridiagonal, its coupling blocks are a diagonal plus their last column.  Small problems keep the dense engine, bit for bit as
+  // before.  A problem over the dense engine's size limit whose ONLY reason for that engine are these costs runs on the block chain
+  // with dense coupling blocks - the pair rows' chain, which carries the costs alone, next to pair rows (velocity limits with time,
+  // LVS / cast collision rows) and next to any other row term (QpWs::tvo, tmx_qp.h).  TMX_VEL_TIME_CHAIN: "1" the chain at any size,
+  // "0" never (the dense engine and its limit).  Next to TotalTime terms, acceleration / jerk costs or rows, or function costs
+  // (their D x D objective blocks live in the per-problem scratch, QpWs::pb, and take another ADMM loop) the dense engine stays.
+  if (tv_terms)
+  {
+    const char* e = std::getenv("TMX_VEL_TIME_CHAIN");
+    const bool able = TMX_LINK_ROWS && !qp_dense && !tt_terms && !stencil_rows && band == 0 && !dyn_p;
+    const bool want = (e && e[0] == '1') || (!(e && e[0] == '0') && P.n_max > dense_qp_max_n());
+    tv_chain = able && want;
+    if (tt_terms)
+      tv_why = " next to TotalTime terms";
+    else if (band != 0 || stencil_rows)
+      tv_why = " next to acceleration / jerk costs or rows";
+    else if (dyn_p)
+      tv_why = " next to function costs";
+    else if (qp_dense || !TMX_LINK_ROWS)
+      tv_why = " in a build without rows on two waypoints";
+    else
+      tv_why = " with TMX_VEL_TIME_CHAIN=0";
+    if (!tv_chain)
+      qp_dense = true;
+    else
+    {
+      st_terms = true;  // (piecewise driver: the costs' linearisations and the QP kernels that carry them are the piecewise kernels')
+      if (R2 == 0)
+        R2 = 1;  // no pair row: one unused second-block slot, so that the workspace has the dense-coupling chain (Cd, Mf, Nb, yb)
+    }
   }
   // Difference ROWS of order 2 / 3 touch one joint each: as long as every row on several waypoints is such a single-joint row (no
   // LVS / cast collision rows, no CartVel rows) all the blocks they add to the reduced KKT matrix are diagonal, and the problem runs
@@ -1374,6 +1410,7 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
   P.st = (qp_dense || st_terms) ? 1 : 0;
   P.tt_chain = tt_chain ? (int)tt_owner.size() : 0;
   P.tt_place = 0;
+  P.tv_chain = tv_chain ? 1 : 0;
   // convex-hull links: their contact code (GJK / EPA) is instantiated in the piecewise kernels only (template flag HULL)
   {
     int n_hull = 0;
@@ -1731,12 +1768,13 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
   // LDS budgets
   ctx->smem_qp = qp_smem_bytes(D, T, R, NA, R2, P.coef_far);
   ctx->tt_scratch = 0;
-  if (P.tt_chain > 0)
+  if (P.tt_chain > 0 || P.tv_chain)
   {
-    // per-problem data of the rank-one terms (g, Z = K_chain^-1 g: read by every ADMM iteration): behind the QP workspace when it
+    // per-problem data of the rank-one terms (g, Z = K_chain^-1 g: read by every ADMM iteration) or the joint - time entries of
+    // squared JointVel-with-time costs (read by every factorisation and every product with P): behind the QP workspace when it
     // stays in LDS with them, or lives in HBM anyway (long horizons); in the per-problem scratch when they alone would push an
     // LDS-resident workspace out
-    const size_t tt_bytes = (qp_tt_doubles(D, T, P.tt_chain) + 2) * sizeof(double);
+    const size_t tt_bytes = ((P.tv_chain ? qp_tv_doubles(D, T) : qp_tt_doubles(D, T, P.tt_chain)) + 2) * sizeof(double);
     const char* force = std::getenv("TMX_TT_PLACE");  // test hook: "2" = in the per-problem scratch whatever the sizes
     if (TMX_QP_COLD_IN_LDS && !(force && force[0] == '2') && (ctx->smem_qp > 160 * 1024 || ctx->smem_qp + tt_bytes <= 160 * 1024))
     {
@@ -1757,8 +1795,9 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
   }
   HIPCHK(hipMemcpy(ctx->dp, &P, sizeof(DevProblem), hipMemcpyHostToDevice));
   if (std::getenv("TMX_VERBOSE"))
-    std::fprintf(stderr, "[tmx] QP engine: %s; TotalTime terms %d, as rank-one terms on the block chain %d (their data %s)\n",
-                 P.qp_dense ? "dense" : (P.st ? "structured, piecewise driver" : "structured"), P.n_tt, P.tt_chain,
+    std::fprintf(stderr, "[tmx] QP engine: %s; TotalTime terms %d, as rank-one terms on the block chain %d; squared velocity-with-time cost instances %d, "
+                         "on the dense-coupling block chain %d (data of either %s)\n",
+                 P.qp_dense ? "dense" : (P.st ? "structured, piecewise driver" : "structured"), P.n_tt, P.tt_chain, P.n_tv, P.tv_chain,
                  P.tt_place == 1 ? "behind the QP workspace" : (P.tt_place == 2 ? "in the per-problem scratch" : "-"));
   if (std::getenv("TMX_VERBOSE"))
     std::fprintf(stderr, "[tmx] problem: D %d (joints %d), T %d, row slots %d, aux %d, pair rows %d, workspace flags %d, band %d, dense %d, QP workspace %zu B, wave-pair solver %d (LDS %zu B, largest lane group %d, second slack in row slots 0x%x)\n", D, P.DK, T, R, NA, R2,
@@ -1786,7 +1825,7 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
       std::string why;
       auto reason = [&why](const std::string& r) { why += (why.empty() ? "" : ", ") + r; };
       if (P.n_tv > 0)
-        reason("squared joint-velocity costs with time");
+        reason("squared joint-velocity costs with time" + tv_why);
       if (stencil_rows)
         reason("acceleration / jerk rows next to collision / CartVel rows on two waypoints or to time-parameterised terms");
       if (tt_terms && (int)tt_owner.size() > TMX_TT_MAX)
@@ -1798,7 +1837,8 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
       if (why.empty())
         reason("acceleration / jerk costs next to rows on two waypoints or function costs");
       ctx->err = why + ": the QP of this problem has too many variables for the dense engine to solve in practical time (limit 448 incl. "
-                 "penalty variables; TMX_DENSE_QP_MAX_N overrides); TotalTime terms alone (up to " + std::to_string(TMX_TT_MAX) + "), function costs, "
+                 "penalty variables; TMX_DENSE_QP_MAX_N overrides); TotalTime terms alone (up to " + std::to_string(TMX_TT_MAX) + "), squared "
+                 "joint-velocity costs with time (alone, next to rows on two waypoints and to other row terms), function costs, "
                  "smoothing costs, acceleration / jerk limits and function terms that are rows (constraints, ABS / HINGE costs, AvoidSingularity, "
                  "DynamicCartPose) have no such limit";
       ctx->have_problem = false;

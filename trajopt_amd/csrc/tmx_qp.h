@@ -254,6 +254,7 @@ struct QpWs
 {
   int D, T, NX, R, NA;
   int DS, DDS;  // row / block stride of Sinv (rows padded to 8 doubles when D <= 8: unmasked 16-byte LDS loads)
+  int tvo;      // (see JOINT - TIME ENTRIES below; in the alignment hole in front of sigma)
   double sigma, alpha, rho, c, cinv;
   // primary (NX)
   double *xp, *zbp, *ybp, *lbp, *ubp, *qp, *Dp, *Ebp, *bbp, *tp, *pd, *po, *dxp, *dybp;
@@ -278,6 +279,17 @@ struct QpWs
   // < 0 behind Da - qp_ws_attach_tt) sit in two alignment holes of this descriptor: its size, and with it the stack frames and the
   // LDS layout of every kernel, are what they were.  ttn is the literal 0 of qp_ws_carve everywhere but in the piecewise QP kernels
   // (qp_solve_block<., ., ROWSK = true>), like pb == nullptr.
+  // JOINT - TIME ENTRIES OF THE OBJECTIVE (squared JointVel-with-time costs on the block chain, DevProblem::tv_chain): exprSquare of
+  // the rows a x[t][j] + b x[t+1][j] + c tau[t+1] + k puts, besides diagonal entries (part of pd) and the (x[t][j], x[t+1][j])
+  // couplings (part of this problem's po), two entries per joint and waypoint between a joint and a TIME variable into P:
+  //   ws_tva(w)[t D + j] = P(x[t][j], tau[t])      inside block t   (the arrow of the block: last row / column)
+  //   ws_tvc(w)[t D + j] = P(x[t][j], tau[t + 1])  between blocks t and t + 1 (last column of the coupling block C_t)
+  // (j < D - 1; the entries at j = D - 1 and those of waypoints without a segment are 0.0), scaled like pd / po.  P stays block
+  // tridiagonal with coupling blocks "diagonal + last column": the problem runs on the dense-coupling chain of the pair rows
+  // (n_link >= 1: Cd, Mf, Nb), kkt_factor adds the entries to the diagonal blocks and to Cd, p_times to every product with P.
+  // tvo != 0 says the entries exist and where (> 0: doubles behind xp, < 0: behind Da - qp_ws_attach_tt, as tto); it is the
+  // literal 0 of qp_ws_carve everywhere but in the piecewise QP kernels, like pb == nullptr and ttn == 0, and sits in an alignment
+  // hole: the descriptor has the size it had.
   // DIFFERENCE ROWS of order 2 / 3 on the banded structured path (DevProblem::band_rows: JointAcc / JointJerk Ineq costs and
   // constraints, trajectory_costs.cpp:556-754, :811-1016): such a row touches ONE joint j on waypoints t .. t + order.  coef / c2
   // hold its entries on t and t + 1 (D-vectors that are zero off joint j), cf[2 i], cf[2 i + 1] (i = the row's c2 index) the
@@ -428,6 +440,50 @@ TMX_DEVFN double tt_p_col_norm(const QpWs& w, int t)
       for (int s = 1; s < w.T; ++s)
         gm = fmax(gm, fabs(g[s]));
       cn = fmax(cn, fabs((ws_ttw(w)[k] * g[t]) * gm));
+    }
+  return cn;
+}
+// ---- joint - time entries of the objective (QpWs::tvo) ------------------------------------------------------------------------
+TMX_HOSTDEVFN size_t qp_tv_doubles(int D, int T) { return 2 * (size_t)D * T; }
+TMX_DEVFN double* ws_tva(const QpWs& w) { return w.tvo > 0 ? w.xp + w.tvo : w.Da - w.tvo; }
+TMX_DEVFN double* ws_tvc(const QpWs& w) { return ws_tva(w) + w.NX; }
+// (P x)_v part of these entries.  One thread forms the sum of a time variable's row, joints ascending, the entries of its own
+// block before those of the coupling: the order does not depend on the number of threads.
+TMX_DEVFN double tv_p_times(const QpWs& w, const double* x, int v)
+{
+  const int D = w.D, t = v / D, j = v % D;
+  const double *va = ws_tva(w), *vc = ws_tvc(w);
+  double s = 0.0;
+  if (j < D - 1)
+  {
+    s = va[v] * x[t * D + D - 1];
+    if (t < w.T - 1)
+      s += vc[v] * x[(t + 1) * D + D - 1];
+  }
+  else
+  {
+    for (int i = 0; i < D - 1; ++i)
+      s += va[t * D + i] * x[t * D + i];
+    if (t > 0)
+      for (int i = 0; i < D - 1; ++i)
+        s += vc[(t - 1) * D + i] * x[(t - 1) * D + i];
+  }
+  return s;
+}
+// largest |entry| these entries put into column v of P
+TMX_DEVFN double tv_p_col_norm(const QpWs& w, int v)
+{
+  const int D = w.D, t = v / D, j = v % D;
+  const double *va = ws_tva(w), *vc = ws_tvc(w);
+  double cn = 0.0;
+  if (j < D - 1)
+    cn = fmax(fabs(va[v]), (t < w.T - 1) ? fabs(vc[v]) : 0.0);
+  else
+    for (int i = 0; i < D - 1; ++i)
+    {
+      cn = fmax(cn, fabs(va[t * D + i]));
+      if (t > 0)
+        cn = fmax(cn, fabs(vc[(t - 1) * D + i]));
     }
   return cn;
 }
@@ -740,6 +796,7 @@ TMX_DEVFN void qp_ws_carve(QpWs& w, double* lds, double* glb, double* far, int D
   w.pb = nullptr;
   w.ttn = 0;
   w.tto = 0;
+  w.tvo = 0;
   w.bk = nullptr;
   w.band_rows = 0;
   w.polish_dd = 0;
@@ -904,16 +961,23 @@ TMX_DEVFN void qp_ws_carve(QpWs& w, double* lds, double* glb, double* far, int D
 #undef TAKEI
 }
 
-// Storage of the rank-one terms over the time variables (DevProblem::tt_chain terms): behind the QP workspace `ws` (LDS, or the
-// HBM slice of a long-horizon problem - tt_place 1) or behind everything else of the per-problem scratch (tt_place 2: the
-// workspace fills the LDS without them)
+// Storage of the rank-one terms over the time variables (DevProblem::tt_chain terms) or of the joint - time entries of the
+// objective (DevProblem::tv_chain; a problem has one of the two): behind the QP workspace `ws` (LDS, or the HBM slice of a
+// long-horizon problem - tt_place 1) or behind everything else of the per-problem scratch (tt_place 2: the workspace fills the LDS
+// without them)
 TMX_DEVFN void qp_ws_attach_tt(QpWs& w, const DevProblem* P, double* ws, double* scratch)
 {
   const int K = P->tt_chain, D = P->D, T = P->T;
   double* p = (P->tt_place == 1) ? ws + ((qp_smem_bytes(D, T, P->R, P->NA, P->n_link, P->coef_far) / sizeof(double) + 1) & ~(size_t)1)
                                  : scratch + ((qp_scratch_doubles(D, T, P->R, P->NA, P->n_link, P->coef_far) + 1) & ~(size_t)1);
-  w.ttn = K;
-  w.tto = (P->tt_place == 1) ? (int)(p - w.xp) : -(int)(p - w.Da);  // (xp: first array of the cold part; Da: in the scratch, and not one of the arrays the polish re-points)
+  const int off = (P->tt_place == 1) ? (int)(p - w.xp) : -(int)(p - w.Da);  // (xp: first array of the cold part; Da: in the scratch, and not one of the arrays the polish re-points)
+  if (P->tv_chain)
+    w.tvo = off;
+  else
+  {
+    w.ttn = K;
+    w.tto = off;
+  }
 }
 
 // row sweep over the slots the workspace says exist: `for r in rows` visits all R slots, or only the active rows when the
@@ -1152,6 +1216,8 @@ TMX_DEVFN void kkt_factor(const QpWs& w, const DevProblem* P, int mode, double s
     }
     else if (w.pb != nullptr)
       s += w.pb[t * DD + i * D + j];
+    else if (w.tvo != 0 && (i == D - 1 || j == D - 1))  // the arrow of the block: P(x[t][.], tau[t])
+      s += ws_tva(w)[t * D + (i < j ? i : j)];
     w.Sinv[t * DDS + i0 * DS + j0] = s;
   }
 #if TMX_LINK_ROWS
@@ -1190,7 +1256,7 @@ TMX_DEVFN void kkt_factor(const QpWs& w, const DevProblem* P, int mode, double s
     for (int e = tid; e < (T - 1) * DD; e += NT)
     {
       const int t = e / DD, i = (e % DD) / D, j = e % D;
-      double c = (i == j) ? w.po[t * D + i] : 0.0;
+      double c = (i == j) ? w.po[t * D + i] : ((w.tvo != 0 && j == D - 1) ? ws_tvc(w)[t * D + i] : 0.0);  // (last column: P(x[t][i], tau[t + 1]))
       for (int q = w.wl_start[t]; q < w.wl_start[t + 1]; ++q)
       {
         const int r = w.wl_list[q];
@@ -1377,6 +1443,11 @@ TMX_DEVFN void chain_pair_products(const QpWs& w, int tid, int NT)
 // independent mat-vec: 2 (T - 1) dependent block steps become 2 (T / P + P) (config 4, T = 30: 58 -> 24; config 3, T = 50: 98 -> 34).
 TMX_DEVFN int pspk_segments(const QpWs& w, int NT)
 {
+  // (problems with joint - time entries of the objective, QpWs::tvo, walk the chain in ONE piece on every build: the spike-corrected
+  //  segments add their products in another order than the plain walk, and the number of segments follows the number of threads -
+  //  these problems keep sums whose order does not depend on it, so that host build, SIMT emulation and device give the same bits)
+  if (w.tvo != 0)
+    return 0;
   const int P = (NT >> 6) < 4 ? (NT >> 6) : 4;
   return (w.WL != nullptr && TMX_HAS_PAIRS(w) && P >= 2 && w.T >= 2 * P + 2 && P * w.D <= 64) ? P : 0;
 }
@@ -2651,6 +2722,8 @@ TMX_DEVFN double p_times(const QpWs& w, const double* x, int v)
     s += w.po[v] * x[v + D];
   if (w.ttn > 0)
     s += tt_p_times(w, x, v);
+  if (w.tvo != 0)
+    s += tv_p_times(w, x, v);
   if (w.band)
   {
     // (exprToEigen's column order is irrelevant for a product; the far couplings follow the near ones)

@@ -46,6 +46,87 @@ struct CscOut
   double *P_x, *q, *A_x, *l, *u;
 };
 
+// ---- squared JointVel-with-time costs: entries of P and q (DevBatch::tv_aff) -----------------------------------------------------
+// exprSquare of the rows a x[t][j] + b x[t+1][j] + c tau[t+1] + k of every instance, scaled by its coefficient; the upper and the lower
+// row of a segment contribute (the lower row's entries are the negated ones).  A triplet exists where a coefficient is not exactly
+// zero (exprToEigen, solver_utils.cpp:49-109); P(i, j) = sum of the triplets, P(j, j) = 2 x sum.  The export (qp_structure) and the
+// load of the block-chain solver (qp_solve_block) both take their values from here: the same operations in the same order.
+// tv_p_val: the entry between two variables of ONE segment sgm of joint jj (-1: every joint) - ia, ib in {0: x[t][j], 1: x[t+1][j],
+// 2: tau[t+1]}
+TMX_DEVFN double tv_p_val(const DevProblem* P, const double* tv_aff, int sgm, int jj, int ia, int ib, bool& any)
+{
+  double v = 0.0;
+  any = false;
+  if (tv_aff == nullptr || sgm < 0 || sgm >= P->T - 1)
+    return v;
+  for (int c = 0; c < P->n_tv; ++c)
+    if ((jj < 0 || P->tv_joint[c] == jj) && sgm >= P->tv_first[c] && sgm < P->tv_last[c])
+    {
+      const double* rec = tv_aff + ((size_t)c * P->T + sgm) * TMX_TV_REC;
+      for (int half = 0; half < 2; ++half)
+      {
+        const double ca = half ? -rec[ia] : rec[ia], cb = half ? -rec[ib] : rec[ib];
+        const double coeff = ((ia == ib) ? ca * ca : 2 * ca * cb) * P->tv_coeff[c];
+        if (coeff != 0.0)
+        {
+          v += (ia == ib) ? 2.0 * coeff : coeff;
+          any = true;
+        }
+      }
+    }
+  return v;
+}
+// tv_p_diag: what the costs add to the diagonal entry of x[t][j], which two segments touch.  Insertion order within a cost: its upper
+// rows by ascending segment - segment t-1 (this variable is x[t+1] of it) before segment t - then its lower rows the same way;
+// duplicates are summed in that order (tripletsToCsc)
+TMX_DEVFN double tv_p_diag(const DevProblem* P, const double* tv_aff, int t, int j, bool& any)
+{
+  double tvd = 0.0;
+  any = false;
+  for (int c = 0; c < P->n_tv; ++c)
+    if (P->tv_joint[c] == j)
+      for (int half = 0; half < 2; ++half)
+        for (int side = 1; side >= 0; --side)
+        {
+          const int sgm = side ? t - 1 : t;
+          if (sgm < P->tv_first[c] || sgm >= P->tv_last[c])
+            continue;
+          const double cfv = tv_aff[((size_t)c * P->T + sgm) * TMX_TV_REC + (side ? 1 : 0)];
+          const double coeff = (cfv * cfv) * P->tv_coeff[c];  // (the lower row's entry is the negated one: same square)
+          if (coeff != 0.0)
+          {
+            tvd += 2.0 * coeff;
+            any = true;
+          }
+        }
+  return tvd;
+}
+// tv_q_lin: qv + the costs' linear terms on variable (t, j) - affexpr of exprSquare (expr_ops.cpp:55-84): 2 * constant * coefficient,
+// scaled by the cost coefficient; exprToVector adds the non-zero ones in insertion order (upper rows of a cost, then its lower rows)
+TMX_DEVFN double tv_q_lin(const DevProblem* P, const double* tv_aff, int t, int j, double qv)
+{
+  for (int c = 0; c < P->n_tv; ++c)
+    for (int half = 0; half < 2; ++half)
+      for (int side = 1; side >= 0; --side)  // segment t-1 (this variable is its x[t+1] / tau[t+1]), then segment t
+      {
+        const int sgm = side ? t - 1 : t;
+        if (sgm < P->tv_first[c] || sgm >= P->tv_last[c])
+          continue;
+        const double* rec = tv_aff + ((size_t)c * P->T + sgm) * TMX_TV_REC;
+        double cf = 0.0;
+        if (j == P->D - 1)
+          cf = side ? rec[2] : 0.0;
+        else if (j == P->tv_joint[c])
+          cf = side ? rec[1] : rec[0];
+        if (half)
+          cf = -cf;
+        const double lin = ((2 * rec[3 + half]) * cf) * P->tv_coeff[c];
+        if (lin != 0.0)
+          qv += lin;
+      }
+  return qv;
+}
+
 // ST: the problem may hold difference rows of order 2 / 3 (entries on waypoints t + 2, t + 3: diff_row_coef) and the banded
 // objective of the acceleration / jerk costs (DevProblem::po2 / po3).  The ST = false instantiation is the code of the
 // block-tridiagonal problems, unchanged.
@@ -422,28 +503,7 @@ TMX_DEVFN void qp_structure(const DevProblem* P, const int* active, const double
       };
       // role of the two Jacobian entries of a velocity-cost record: ia, ib in {0: x[t][j], 1: x[t+1][j], 2: tau[t+1]} of segment sgm of
       // joint jj; the upper and the lower row of every instance contribute (the lower row's entries are the negated ones)
-      auto tv_val = [&](int sgm, int jj, int ia, int ib, bool& any) -> double {
-        double v = 0.0;
-        any = false;
-        if (tv_aff == nullptr || sgm < 0 || sgm >= P->T - 1)
-          return v;
-        for (int c = 0; c < P->n_tv; ++c)
-          if ((jj < 0 || P->tv_joint[c] == jj) && sgm >= P->tv_first[c] && sgm < P->tv_last[c])
-          {
-            const double* rec = tv_aff + ((size_t)c * P->T + sgm) * TMX_TV_REC;
-            for (int half = 0; half < 2; ++half)
-            {
-              const double ca = half ? -rec[ia] : rec[ia], cb = half ? -rec[ib] : rec[ib];
-              const double coeff = ((ia == ib) ? ca * ca : 2 * ca * cb) * P->tv_coeff[c];
-              if (coeff != 0.0)
-              {
-                v += (ia == ib) ? 2.0 * coeff : coeff;
-                any = true;
-              }
-            }
-          }
-        return v;
-      };
+      auto tv_val = [&](int sgm, int jj, int ia, int ib, bool& any) -> double { return tv_p_val(P, tv_aff, sgm, jj, ia, ib, any); };
       auto tt_val = [&](int s_, int t_, bool& any) -> double {  // time variables of waypoints s_ <= t_
         double v = 0.0;
         any = false;
@@ -491,26 +551,7 @@ TMX_DEVFN void qp_structure(const DevProblem* P, const int* active, const double
           double tvd = 0.0;
           any2 = false;
           if (P->use_time && tv_aff != nullptr)
-          {
-            // insertion order within a cost: its upper rows by ascending segment - segment t-1 (this variable is x[t+1] of it) before
-            // segment t - then its lower rows the same way; duplicates are summed in that order (tripletsToCsc)
-            for (int c2_ = 0; c2_ < P->n_tv; ++c2_)
-              if (P->tv_joint[c2_] == j)
-                for (int half = 0; half < 2; ++half)
-                  for (int side = 1; side >= 0; --side)
-                  {
-                    const int sgm = side ? t - 1 : t;
-                    if (sgm < P->tv_first[c2_] || sgm >= P->tv_last[c2_])
-                      continue;
-                    const double cfv = tv_aff[((size_t)c2_ * P->T + sgm) * TMX_TV_REC + (side ? 1 : 0)];
-                    const double coeff = (cfv * cfv) * P->tv_coeff[c2_];  // (the lower row's entry is the negated one: same square)
-                    if (coeff != 0.0)
-                    {
-                      tvd += 2.0 * coeff;
-                      any2 = true;
-                    }
-                  }
-          }
+            tvd = tv_p_diag(P, tv_aff, t, j, any2);
           if (P->pd[c] != 0.0 || any || any2)
             f(c, (P->pd[c] + dv) + tvd);
           return;
@@ -694,25 +735,7 @@ TMX_DEVFN void qp_structure(const DevProblem* P, const int* active, const double
           // the non-zero ones in insertion order (upper rows of a cost, then its lower rows)
           const int t = v / D, j = v % D;
           if (tv_aff != nullptr)
-            for (int c = 0; c < P->n_tv; ++c)
-              for (int half = 0; half < 2; ++half)
-                for (int side = 1; side >= 0; --side)  // segment t-1 (this variable is its x[t+1] / tau[t+1]), then segment t
-                {
-                  const int sgm = side ? t - 1 : t;
-                  if (sgm < P->tv_first[c] || sgm >= P->tv_last[c])
-                    continue;
-                  const double* rec = tv_aff + ((size_t)c * P->T + sgm) * TMX_TV_REC;
-                  double cf = 0.0;
-                  if (j == D - 1)
-                    cf = side ? rec[2] : 0.0;
-                  else if (j == P->tv_joint[c])
-                    cf = side ? rec[1] : rec[0];
-                  if (half)
-                    cf = -cf;
-                  const double lin = ((2 * rec[3 + half]) * cf) * P->tv_coeff[c];
-                  if (lin != 0.0)
-                    qv += lin;
-                }
+            qv = tv_q_lin(P, tv_aff, t, j, qv);
           if (tt_aff != nullptr && j == D - 1 && t >= 1)
             for (int c = 0; c < P->n_tt; ++c)
               if (P->tt_form[c] == 0)
@@ -1316,7 +1339,7 @@ __device__ __attribute__((noinline)) static void qp_admm_generic_nl(const DevPro
     if (HBM && __builtin_amdgcn_readfirstlane(chain_in_lds) != 0)
       qp_ws_chain_to_lds(w, lds);
     if constexpr (TT)
-      qp_ws_attach_tt(w, P, smem, scratch);
+      qp_ws_attach_tt(w, P, smem, scratch);  // (or the joint - time entries of squared JointVel-with-time costs: QpWs::tvo)
   }
 #if TMX_LINK_ROWS
   w.c2i = P->slot_c2;
@@ -1398,8 +1421,9 @@ TMX_DEVFN void qp_solve_block(const DevProblem* P, const DevBatch* Bt, int b, do
       dyn_g = Bt->fx_g + (size_t)b * P->n_fx_cost * D;
     }
   // TotalTime terms on the block chain (piecewise kernels only): rank-one terms over the time variables
+  // ... and squared JointVel-with-time costs on it: the objective's entries between joints and time variables (QpWs::tvo)
   if constexpr (ROWSK)
-    if (P->tt_chain > 0)
+    if (P->tt_chain > 0 || P->tv_chain)
       qp_ws_attach_tt(w, P, smem, Bt->qp_scratch + (size_t)b * Bt->qp_scratch_stride);
   long long pc[16] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
   long long tlast = TMX_CLK();
@@ -1525,6 +1549,32 @@ TMX_DEVFN void qp_solve_block(const DevProblem* P, const DevBatch* Bt, int b, do
         w.qp[v] = qv;
       }
     w.po[v] = (v < NX - D) ? P->po[v] : 0.0;
+    if constexpr (ROWSK)
+      if (w.tvo != 0)
+      {
+        // squared JointVel-with-time costs (tv_p_val / tv_p_diag / tv_q_lin: the values of qp_structure's export): diagonal entries into
+        // pd, the (x[t][j], x[t+1][j]) couplings into this problem's po, the entries on the time variables into tva / tvc
+        const int t = v / D;
+        const double* aff = Bt->tv_aff + (size_t)b * P->n_tv * T * TMX_TV_REC;
+        bool any;
+        double va = 0.0, vc = 0.0;
+        if (j < D - 1)
+        {
+          w.pd[v] = P->pd[v] + tv_p_diag(P, aff, t, j, any);
+          if (v < NX - D)
+          {
+            w.po[v] = P->po[v] + tv_p_val(P, aff, t, j, 0, 1, any);
+            vc = tv_p_val(P, aff, t, j, 0, 2, any);
+          }
+          if (t >= 1)
+            va = tv_p_val(P, aff, t - 1, j, 1, 2, any);
+        }
+        else if (t >= 1)
+          w.pd[v] = P->pd[v] + tv_p_val(P, aff, t - 1, -1, 2, 2, any);
+        ws_tva(w)[v] = va;
+        ws_tvc(w)[v] = vc;
+        w.qp[v] = tv_q_lin(P, aff, t, j, w.qp[v]);
+      }
     if (w.band)
     {
       w.po2[v] = (v < NX - 2 * D) ? P->po2[v] : 0.0;
@@ -1642,6 +1692,8 @@ TMX_DEVFN void qp_solve_block(const DevProblem* P, const DevBatch* Bt, int b, do
       if (w.pb != nullptr)
         for (int i = 0; i < D; ++i)
           cn = fmax(cn, fabs(w.pb[(size_t)t * D * D + i * D + j]));
+      if (w.tvo != 0)
+        cn = fmax(cn, tv_p_col_norm(w, v));
       {
         // (groups of four: the three dependent loads per list entry - slot, active flag, coefficient - of four entries are in flight
         //  together; a maximum does not depend on the order.  The coefficient of an inactive slot may be uninitialised: selected away)
@@ -1757,6 +1809,14 @@ TMX_DEVFN void qp_solve_block(const DevProblem* P, const DevBatch* Bt, int b, do
         const int t = e / (D * D), i = (e / D) % D, j = e % D;
         w.pb[e] = (w.tp[t * D + i] * w.pb[e]) * w.tp[t * D + j];
       }
+    if (w.tvo != 0)
+      for (int v = tid; v < NX; v += NT)
+      {
+        const int t = v / D;
+        ws_tva(w)[v] = (w.tp[v] * ws_tva(w)[v]) * w.tp[t * D + D - 1];
+        if (t < T - 1)
+          ws_tvc(w)[v] = (w.tp[v] * ws_tvc(w)[v]) * w.tp[(t + 1) * D + D - 1];
+      }
     TMX_ROWS(w, r)
     {
       if (!w.act[r])
@@ -1805,6 +1865,8 @@ TMX_DEVFN void qp_solve_block(const DevProblem* P, const DevBatch* Bt, int b, do
           cn = fmax(cn, fabs(w.pb[(size_t)t * D * D + i * D + v % D]));
       if (w.ttn > 0 && v % D == D - 1)
         cn = fmax(cn, tt_p_col_norm(w, t));
+      if (w.tvo != 0)
+        cn = fmax(cn, tv_p_col_norm(w, v));
       w.tp[v] = cn;
       qmax = fmax(qmax, fabs(w.qp[v]));
     }
@@ -1855,6 +1917,9 @@ TMX_DEVFN void qp_solve_block(const DevProblem* P, const DevBatch* Bt, int b, do
     if (w.ttn > 0 && tid == 0)
       for (int k = 0; k < w.ttn; ++k)
         ws_ttw(w)[k] *= ct;
+    if (w.tvo != 0)
+      for (int v = tid; v < 2 * NX; v += NT)
+        ws_tva(w)[v] *= ct;  // (tva | tvc)
     TMX_ROWS(w, r)
       if (w.act[r])
         for (int k = 0; k < w.naux[r]; ++k)
@@ -1958,7 +2023,7 @@ TMX_DEVFN void qp_solve_block(const DevProblem* P, const DevBatch* Bt, int b, do
   // ---------------- factor + ADMM loop (osqp_solve) --------------------------------------------------------
   TMX_TICK(0);
 #if TMX_IS_DEVICE
-  const bool fast = TMX_UNI_B(!HBM && (NT == TMX_QP_NT) && (R <= 512) && dpart_supported(w, NT) && !TMX_HAS_PAIRS(w) && w.c_alist == nullptr && w.band == 0 && w.pb == nullptr && w.ttn == 0 && TMX_FAST_ALLOWED);
+  const bool fast = TMX_UNI_B(!HBM && (NT == TMX_QP_NT) && (R <= 512) && dpart_supported(w, NT) && !TMX_HAS_PAIRS(w) && w.c_alist == nullptr && w.band == 0 && w.pb == nullptr && w.ttn == 0 && w.tvo == 0 && TMX_FAST_ALLOWED);
 #else
   const bool fast = false;
 #endif
@@ -2050,7 +2115,7 @@ TMX_DEVFN void qp_solve_block(const DevProblem* P, const DevBatch* Bt, int b, do
     {
       // instantiations: with / without pair rows; block size 7 (7-DOF arms: configs 2 and 4) and, for the HBM-workspace pair-row
       // problems, 10 (config 3) as compile-time constants
-      if (ROWSK && w.ttn > 0)  // TotalTime terms on the block chain (never with a banded objective: tmx_problem_upload)
+      if (ROWSK && (w.ttn > 0 || w.tvo != 0))  // TotalTime terms / squared JointVel-with-time costs on the block chain (never with a banded objective: tmx_problem_upload; with the costs n_link >= 1)
       {
         if (P->n_link > 0)
           qp_admm_generic_nl<HBM, true, 0, false, true>(P, Bt, b, lds_off, HBM ? smem : nullptr, chain_lds != nullptr ? 1 : 0);

@@ -158,6 +158,12 @@ struct DevProblem
   // the terms as rank-one corrections of the reduced KKT matrix (QpWs::ttn); tt_place: where the per-problem data of the
   // correction live (qp_ws_attach_tt).  0 everywhere else.  (Last: the offsets of the fields above are what they were.)
   int tt_chain, tt_place;
+  // Squared JointVel-with-time costs ON THE BLOCK CHAIN (tmx_problem_upload: the only reason for the dense engine are these costs and
+  // the QP is over its size limit, or TMX_VEL_TIME_CHAIN=1): tv_chain = 1 and qp_dense = 0 - the piecewise QP kernels carry the
+  // entries the costs put between a joint and the time variables (QpWs::tvo) on the dense-coupling chain; n_link is then at least 1
+  // (a problem without pair rows gets one unused second-block slot: the chain with dense coupling blocks is the pair-row code).
+  // tt_place says where the per-problem entries live (never next to TotalTime terms on the chain).  0 everywhere else.
+  int tv_chain;
 };
 TMX_HOSTDEVFN int slot_is_diff(int kind) { return kind == SLOT_JOINTVEL || kind == SLOT_JOINTVEL_INEQ; }
 #define TMX_TV_REC 5  // DevBatch::tv_aff record of one segment: cleaned Jacobian entries on x[t][j], x[t+1][j], tau[t+1] (upper row), constants of the upper / lower row

@@ -1735,6 +1735,31 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
       }
     }
   }
+  P.wp_pst = P.row_epos = nullptr;
+  P.setup_fast = 0;
+  {
+    // constants of the QP setup (DevProblem::wp_pst / row_epos): the grouped e exchange of the register-resident burst keeps the rows of
+    // waypoint t in wp_list order from the even offset wp_pst[t] on
+    std::vector<int> pst(T + 1, 0), epos(R, 0);
+    int acc = 0, rows_max = 0, naux_max = 0;
+    for (int t = 0; t <= T; ++t)
+    {
+      pst[t] = acc;
+      if (t == T)
+        break;
+      const int c = wp_start[t + 1] - wp_start[t];
+      for (int u = wp_start[t]; u < wp_start[t + 1]; ++u)
+        epos[wp_list[u]] = acc + (u - wp_start[t]);
+      acc += c + (c & 1);
+      rows_max = std::max(rows_max, c);
+    }
+    for (int r = 0; r < R; ++r)
+      naux_max = std::max(naux_max, naux[r]);
+    tmx_status rcs;
+    if ((rcs = upload(ctx, ctx->prob_allocs, &P.wp_pst, pst)) != TMX_OK || (rcs = upload(ctx, ctx->prob_allocs, &P.row_epos, epos)) != TMX_OK)
+      return rcs;
+    P.setup_fast = (rows_max <= TMX_SETUP_COL && naux_max <= 2 && R <= 2 * TMX_QP_NT) ? 1 : 0;
+  }
 #if TMX_IS_DEVICE
   {
     // OPT-IN (TMX_WAVE=1): measured on MI355X (round 6, profiles/r06/) the wave-pair solver runs BASELINE config 1 at 101 k SQP it/s
@@ -3286,6 +3311,15 @@ __attribute__((visibility("default"))) tmx_status tmx_debug_set_flags(tmx_ctx* c
   ctx->hp.dbg_flags = flags;
   HIPCHK(hipMemcpy(reinterpret_cast<char*>(ctx->dp) + offsetof(DevProblem, dbg_flags), &flags, sizeof(int), hipMemcpyHostToDevice));
   return TMX_OK;
+}
+
+// debug hook (not in include/tmx.h): 1 when the uploaded problem qualifies for the register-resident QP setup of the dense fast path
+// (DevProblem::setup_fast; the kernels add their own fast-path predicate), 0 when not, -1 without a problem
+__attribute__((visibility("default"))) int tmx_debug_setup_fast(tmx_ctx* ctx)
+{
+  if (!ctx || !ctx->have_problem)
+    return -1;
+  return ctx->hp.setup_fast;
 }
 
 // debug hook (not in include/tmx.h): 1 = fused persistent optimize() kernel (default), 0 = one launch chain per step

@@ -2,6 +2,7 @@
 // BasicTrustRegionSQP state machine (K6 decisions).  See tmx_qp.h for the KKT algebra.
 #pragma once
 #include "tmx_qp.h"
+#include "tmx_setup.h"
 #include "tmx_terms.h"
 
 #if TMX_IS_DEVICE
@@ -1071,6 +1072,30 @@ TMX_DEVFN T* tmx_uniform_ptr(T* p)
   const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
   return (T*)(((unsigned long long)hi << 32) | lo);
 }
+// The register-resident Ruiz scaling of the dense fast path (tmx_setup.h) as a function of its own, entered once per QP solve: its ~130
+// registers of matrix entries do not join the allocation of the kernel's cold code.  TMX_SETUP_OUTLINED=0 compiles it inline (A/B switch).
+#ifndef TMX_SETUP_OUTLINED
+#define TMX_SETUP_OUTLINED 1
+#endif
+#if TMX_SETUP_OUTLINED
+__device__ __attribute__((noinline)) static double qp_ruiz_fast_nl(const DevProblem* P_in, const DevBatch* Bt_in, int b_in, unsigned lds_in)
+{
+  const DevProblem* P = tmx_uniform_ptr(P_in);
+  const DevBatch* Bt = tmx_uniform_ptr(Bt_in);
+  const int b = __builtin_amdgcn_readfirstlane(b_in);
+  const int tid = threadIdx.x;
+  double* smem = (double*)(tmx_lds_d*)(size_t)(unsigned)__builtin_amdgcn_readfirstlane((int)lds_in);
+  const int D = P->D, T = P->T, R = P->R;
+  double* scratch = Bt->qp_scratch + (size_t)b * Bt->qp_scratch_stride;
+  QpWs w;
+#if TMX_QP_COLD_IN_LDS
+  qp_ws_carve(w, smem, smem + qp_lds_doubles(D, T, R, P->NA, P->n_link), scratch, D, T, R, P->NA, P->n_link, P->coef_far);
+#else
+  qp_ws_carve(w, smem, scratch + qp_far_doubles(D, T, R, P->NA, P->n_link, P->coef_far), scratch, D, T, R, P->NA, P->n_link, P->coef_far);
+#endif
+  return ruiz_fast(w, P, P->osqp.scaling, Bt->dims[4 * b], tid);
+}
+#endif
 // between two bursts (iteration `iter` just done): returns 1 when the loop ends
 // (the workgroup's dynamic LDS base travels as a 32-bit LDS offset: no extern __shared__ lookup inside the callees)
 __device__ __attribute__((noinline)) static int qp_check_nl(const DevProblem* P_in, const DevBatch* Bt_in, int b_in, int iter_in, unsigned lds_in)
@@ -1437,10 +1462,21 @@ TMX_DEVFN void qp_solve_block(const DevProblem* P, const DevBatch* Bt, int b, do
   const int* dims = Bt->dims + 4 * b;
   const unsigned long long* hs = Bt->hashes + 4 * b;
 
+  // the dense fast path (every term is known at entry), and its setup: the per-problem constants of the load from the upload, prefix
+  // counts by wave ballots, the Ruiz scaling in registers (tmx_setup.h).  DevProblem::dbg_flags bit 1 keeps the generic setup: same bits
+#if TMX_IS_DEVICE
+  const bool fast = TMX_UNI_B(!HBM && (NT == TMX_QP_NT) && (R <= 512) && dpart_supported(w, NT) && !TMX_HAS_PAIRS(w) && w.c_alist == nullptr && w.band == 0 && w.pb == nullptr && w.ttn == 0 && w.tvo == 0 && TMX_FAST_ALLOWED);
+  const bool fast_setup = TMX_UNI_B(fast && P->setup_fast != 0 && !(P->dbg_flags & 2));
+#else
+  const bool fast = false;
+  const bool fast_setup = false;
+#endif
   // ---------------- load (unscaled) --------------------------------------------------------------------
   for (int r = tid; r < R; r += NT)
   {
     w.act[r] = g_act[r];
+    if (fast_setup)
+      w.row_epos[r] = P->row_epos[r];
     w.naux[r] = P->slot_naux[r];
     w.aoff[r] = P->slot_aoff[r];
     w.slot_t[r] = P->slot_t[r];
@@ -1609,6 +1645,11 @@ TMX_DEVFN void qp_solve_block(const DevProblem* P, const DevBatch* Bt, int b, do
   for (int t = tid; t <= T; t += NT)
   {
     w.wp_start[t] = P->wp_start[t];
+    if (fast_setup)
+    {
+      w.wp_pst[t] = P->wp_pst[t];
+      continue;
+    }
     int acc = 0;  // even-padded group starts of the grouped e exchange
     for (int u = 0; u < t; ++u)
     {
@@ -1638,12 +1679,37 @@ TMX_DEVFN void qp_solve_block(const DevProblem* P, const DevBatch* Bt, int b, do
       int cnt = 0;
       for (int r = r0; r < r1; ++r)
         cnt += w.act[r] ? (pass == 0 ? 1 : w.naux[r]) : 0;
-      TMX_SYNC();
-      scan[tid] = cnt;
-      TMX_SYNC();
       int off = 0;
-      for (int u = 0; u < tid; ++u)
-        off += scan[u];
+#if TMX_IS_DEVICE
+      if (fast_setup)
+      {
+        // exclusive prefix inside the wave by ballots of the count's bits (C <= 2 slots with at most two slack variables each: the count
+        // is below 8), then the totals of the waves below; integers - any order is exact
+        const int lane = tid & 63, wave = tid >> 6;
+        const unsigned long long below = (1ull << lane) - 1ull;
+        int tot = 0;
+        for (int bit = 0; bit < 3; ++bit)
+        {
+          const unsigned long long mk = __builtin_amdgcn_ballot_w64(((cnt >> bit) & 1) != 0);
+          off += __builtin_popcountll(mk & below) << bit;
+          tot += __builtin_popcountll(mk) << bit;
+        }
+        TMX_SYNC();
+        if (lane == 0)
+          scan[wave] = tot;
+        TMX_SYNC();
+        for (int u = 0; u < wave; ++u)
+          off += scan[u];
+      }
+      else
+#endif
+      {
+        TMX_SYNC();
+        scan[tid] = cnt;
+        TMX_SYNC();
+        for (int u = 0; u < tid; ++u)
+          off += scan[u];
+      }
       for (int r = r0; r < r1; ++r)
       {
         if (pass == 0)
@@ -1665,7 +1731,7 @@ TMX_DEVFN void qp_solve_block(const DevProblem* P, const DevBatch* Bt, int b, do
   double* const t_eba = lds_tmp ? w.G + NX : w.dyba;
   double* const t_da = lds_tmp ? w.G + NX + P->NA : w.ta;
   double* const acc_da = lds_tmp ? w.G + NX + 2 * P->NA : w.Da;  // running D scaling of the aux vars
-  if (lds_tmp)
+  if (lds_tmp && !fast_setup)
   {
     for (int a = tid; a < P->NA; a += NT)
       acc_da[a] = 1.0;
@@ -1676,6 +1742,21 @@ TMX_DEVFN void qp_solve_block(const DevProblem* P, const DevBatch* Bt, int b, do
   TMX_TICK(13);
 #endif
   // ---------------- Ruiz equilibration (scale_data) ------------------------------------------------------
+#if TMX_IS_DEVICE
+  if (fast_setup)
+  {
+#if TMX_ADMM_OUTLINED && TMX_SETUP_OUTLINED
+    unsigned lds_off = (unsigned)(size_t)smem;  // (opaque: see the call of qp_admm_fast_nl below)
+    TMX_ASM_OPAQUE_SGPR(lds_off);
+    w.c = qp_ruiz_fast_nl(P, Bt, b, lds_off);
+#else
+    w.c = ruiz_fast(w, P, st.scaling, n, tid);
+#endif
+    w.cinv = 1.0 / w.c;
+  }
+  else
+#endif
+  {
   // temporaries: D_temp_p -> tp, D_temp_a -> ta, E_temp_r -> hr, E_temp_bp -> dybp, E_temp_ba -> dyba
   for (int it = 0; it < st.scaling; ++it)
   {
@@ -1948,6 +2029,7 @@ TMX_DEVFN void qp_solve_block(const DevProblem* P, const DevBatch* Bt, int b, do
       w.typ_ba[w.aoff[r] + k] = constr_type(0.0, TMX_OSQP_INFTY * w.Eba[w.aoff[r] + k]);
   }
   TMX_SYNC();
+  }
 
 #if defined(TMX_FINE) && TMX_FINE == 4
   TMX_TICK(15);
@@ -2022,11 +2104,6 @@ TMX_DEVFN void qp_solve_block(const DevProblem* P, const DevBatch* Bt, int b, do
 
   // ---------------- factor + ADMM loop (osqp_solve) --------------------------------------------------------
   TMX_TICK(0);
-#if TMX_IS_DEVICE
-  const bool fast = TMX_UNI_B(!HBM && (NT == TMX_QP_NT) && (R <= 512) && dpart_supported(w, NT) && !TMX_HAS_PAIRS(w) && w.c_alist == nullptr && w.band == 0 && w.pb == nullptr && w.ttn == 0 && w.tvo == 0 && TMX_FAST_ALLOWED);
-#else
-  const bool fast = false;
-#endif
 #if TMX_IS_DEVICE
   if (fast)
     qp_ws_alias_deltas(w, P, dpt);

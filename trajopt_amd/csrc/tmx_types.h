@@ -151,7 +151,8 @@ struct DevProblem
   // with two slack variables each per thread.  nullptr: thread tid holds row tid, the rows beyond 256 sit on the last threads
   int* row_perm;
   // diagnostic switches (tmx_debug_set_flags, not part of include/tmx.h): bit 0 = the D x D diagonal blocks of the reduced KKT matrix by
-  // the scalar list-order loop instead of v_mfma_f64_16x16x4_f64 (tests/test_gpu_parity.py compares the two on the same QP)
+  // the scalar list-order loop instead of v_mfma_f64_16x16x4_f64 (tests/test_gpu_parity.py compares the two on the same QP);
+  // bit 1 = the generic load and Ruiz scaling of the QP setup on a problem of the dense fast path (setup_fast below)
   int dbg_flags;
   // TotalTime terms ON THE BLOCK CHAIN (tmx_problem_upload: the only reason for the dense engine are these terms and the QP is over
   // its size limit, or TMX_TOTAL_TIME_CHAIN=1): tt_chain = n_tt (<= TMX_TT_MAX) and qp_dense = 0 - the structured QP kernels carry
@@ -164,6 +165,13 @@ struct DevProblem
   // (a problem without pair rows gets one unused second-block slot: the chain with dense coupling blocks is the pair-row code).
   // tt_place says where the per-problem entries live (never next to TotalTime terms on the chain).  0 everywhere else.
   int tv_chain;
+  // CONSTANTS OF THE QP SETUP, built at upload next to row_perm (they depend on wp_start / wp_list only; every QP solve used to
+  // recompute them): wp_pst[t] (T + 1) = even-padded start of waypoint t's group in the grouped e exchange of the burst, row_epos[r]
+  // (R) = position of row slot r in it.  setup_fast: the register-resident Ruiz scaling of the dense fast path (tmx_setup.h) can take
+  // the problem - no waypoint with more rows than its column cache, at most two slack variables per row.  dbg_flags bit 1 selects the
+  // generic load and Ruiz on such a problem (same bits; tests/test_fast_setup.py compares the two in one library).
+  int *wp_pst, *row_epos;
+  int setup_fast;
 };
 TMX_HOSTDEVFN int slot_is_diff(int kind) { return kind == SLOT_JOINTVEL || kind == SLOT_JOINTVEL_INEQ; }
 #define TMX_TV_REC 5  // DevBatch::tv_aff record of one segment: cleaned Jacobian entries on x[t][j], x[t+1][j], tau[t+1] (upper row), constants of the upper / lower row
@@ -230,6 +238,9 @@ struct DevBatch
   double *tv_aff, *tt_aff;
 };
 
+// rows of a waypoint the register-resident Ruiz scaling keeps per column (tmx_setup.h); the grouped e buffer (QpWs::hr) is padded by
+// as many entries, which is what the burst's own column cache reads (16 + 2 TMX_CJX, tmx_part.h)
+#define TMX_SETUP_COL 18
 // The ADMM loop of the dense fast path as separately compiled device functions (tmx_solve.h: qp_admm_fast_nl /
 // qp_check_nl).  Default on for the device build.
 #ifndef TMX_ADMM_OUTLINED

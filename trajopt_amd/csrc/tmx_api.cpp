@@ -11,6 +11,8 @@
 #include "tmx_kernels.h"
 #include "tmx_wave_kernels.h"
 #include "tmx_wave_plan.h"
+#include "tmx_row_perm.h"
+#include "tmx_upload.h"
 
 #ifdef TMX_HOST_EMU
 #include <chrono>
@@ -81,14 +83,6 @@ struct tmx_ctx
   size_t best_cap{ 0 };
   int max_rec{ 128 };
 };
-
-// size limit of the dense QP engine (QP variables incl. penalty variables); TMX_DENSE_QP_MAX_N lifts it for callers who accept the time
-static int dense_qp_max_n()
-{
-  if (const char* e = std::getenv("TMX_DENSE_QP_MAX_N"))
-    return std::max(1, std::atoi(e));
-  return 448;
-}
 
 template <typename T>
 static tmx_status upload(tmx_ctx* ctx, std::vector<void*>& pool, T** dst, const std::vector<T>& src)
@@ -265,52 +259,12 @@ void tmx_destroy(tmx_ctx* ctx)
 
 const char* tmx_last_error(const tmx_ctx* ctx) { return ctx ? ctx->err.c_str() : "null context"; }
 
-tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx_sqp_params* sqp, const tmx_osqp_settings* osqp)
+// ---- tmx_problem_upload: the description -> DevProblem, in five stages (tmx_upload.h) ----
+
+// the waypoint layout, the kinematic chain and the solver parameters
+static void fill_basic_info(const tmx_problem_desc* d, const tmx_sqp_params* sqp, const tmx_osqp_settings* osqp, DevProblem& P)
 {
-  if (!ctx || !d)
-    return TMX_ERR_INVALID;
-  TMX_REFUSE_WHILE_PENDING(ctx);
-  HIPCHK(hipSetDevice(ctx->device));
-  // DK joints; D variables per waypoint (time-parameterised problems carry the time variable 1 / dt behind the joints)
-  const int DK = d->n_dof, T = d->n_steps;
-  const int D = DK + (d->use_time ? 1 : 0);
-  if (DK < 1 || D > TMX_MAX_DOF || T < 1)
-  {
-    ctx->err = "n_dof (+ 1 with use_time) must be in [1, TMX_MAX_DOF] and n_steps >= 1";
-    return TMX_ERR_INVALID;
-  }
-  if (d->use_time && (d->dt_lower_lim <= 0 || d->dt_upper_lim < d->dt_lower_lim))
-  {
-    // ProblemConstructionInfo::readBasicInfo  problem_description.cpp:129-133
-    ctx->err = "dt limits (Basic Info) invalid. The lower limit must be positive, and the minimum upper limit is equal to the lower limit.";
-    return TMX_ERR_INVALID;
-  }
-  {
-    // ConstructProblem  problem_description.cpp:415-452: a term that uses time <=> basic_info.use_time
-    bool term_time = false;
-    for (int k = 0; k < d->n_terms && d->terms; ++k)
-      term_time = term_time || d->terms[k].kind == TMX_TERM_JOINT_VEL_TIME || d->terms[k].kind == TMX_TERM_TOTAL_TIME;
-    if (term_time && !d->use_time)
-    {
-      ctx->err = "A term is using time and basic_info is not set correctly. Try basic_info.use_time = true";
-      return TMX_ERR_INVALID;
-    }
-    // (the converse - "No terms use time and basic_info is not set correctly" - is a check on the TermInfo FLAGS in the reference: a
-    //  joint_pos term listed with use_time switches the time column on without ever touching it, problem_description.cpp:1124-1125;
-    //  the front ends make that check, the term table cannot)
-  }
-  if (d->n_fixed_steps < 0 || d->n_fixed_dofs < 0 || d->n_terms < 0 || d->n_link_spheres < 0 || d->n_obstacles < 0 ||
-      (d->n_fixed_steps > 0 && !d->fixed_steps) || (d->n_fixed_dofs > 0 && !d->fixed_dofs) || (d->n_terms > 0 && !d->terms) ||
-      (d->n_link_spheres > 0 && !d->link_spheres) || (d->n_obstacles > 0 && !d->obstacles))
-  {
-    ctx->err = "tmx_problem_desc: negative count or NULL array with a positive count";
-    return TMX_ERR_INVALID;
-  }
-  free_pool(ctx->prob_allocs);
-  free_pool(ctx->batch_allocs);
-  ctx->Bcap = 0;
-  ctx->have_problem = false;
-  DevProblem& P = ctx->hp;
+  const int DK = d->n_dof, T = d->n_steps, D = DK + (d->use_time ? 1 : 0);
   std::memset(&P, 0, sizeof(P));
   P.D = D;
   P.DK = DK;
@@ -348,43 +302,43 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
     P.osqp = *osqp;
   else
     tmx_default_osqp_settings(&P.osqp);
+}
 
+// Stage 1: validates the description and lowers the terms into the row-slot template, the static Hessian and the per-kind tables;
+// then the waypoint grouping of the slots and the geometry tables.  No HIP call; writes the counts into P.
+static tmx_status lower_terms(const tmx_problem_desc* d, DevProblem& P, Lowered& L, std::string& err)
+{
+  const int DK = P.DK, D = P.D, T = P.T;
   // ---- slot template in reference row order ----
-  std::vector<int> kind, st, sub, sub2, owner, naux, iscnt, iseq;
-  std::vector<double> objc, scale, aux1, aux2;
-  std::vector<int> c2, sub3;   // pair rows: index of the second coefficient block; LVS flags
-  std::vector<double> aux3;
-  int R2 = 0, lvs_kmax = 2;
   auto add_slot = [&](int k, int t, int s1, int s2, int own, int na, int isc, int eq, double oc, double sc, double a1, double a2) {
-    kind.push_back(k);
-    st.push_back(t);
-    sub.push_back(s1);
-    sub2.push_back(s2);
-    owner.push_back(own);
-    naux.push_back(na);
-    iscnt.push_back(isc);
-    iseq.push_back(eq);
-    objc.push_back(oc);
-    scale.push_back(sc);
-    aux1.push_back(a1);
-    aux2.push_back(a2);
-    c2.push_back(-1);
-    sub3.push_back(0);
-    aux3.push_back(0.0);
+    L.kind.push_back(k);
+    L.st.push_back(t);
+    L.sub.push_back(s1);
+    L.sub2.push_back(s2);
+    L.owner.push_back(own);
+    L.naux.push_back(na);
+    L.iscnt.push_back(isc);
+    L.iseq.push_back(eq);
+    L.objc.push_back(oc);
+    L.scale.push_back(sc);
+    L.aux1.push_back(a1);
+    L.aux2.push_back(a2);
+    L.c2.push_back(-1);
+    L.sub3.push_back(0);
+    L.aux3.push_back(0.0);
   };
   // DiscreteCollisionEvaluator (evaluator_type 2) / CastCollisionEvaluator (3, 4): one term per SEGMENT (i, i+1)
   // (problem_description.cpp:1720-1761, :1779-1819); per (link sphere, obstacle) max_substates row slots in the order of the
   // flattened contact map (pair-major, sub-state ascending).  Cost and constraint forms share this construction.
-  int n_costs = 0, n_cnts = 0;
   auto add_lvs_segments = [&](const tmx_term& tm) -> tmx_status {
 #if !TMX_LINK_ROWS
     (void)tm;
-    ctx->err = "rows on two consecutive waypoints (LVS / continuous collision) are not enabled in this build";
+    err = "rows on two consecutive waypoints (LVS / continuous collision) are not enabled in this build";
     return TMX_ERR_UNSUPPORTED;
 #else
     if (!(tm.longest_valid_segment_length >= 0))
     {
-      ctx->err = "collision: longest_valid_segment_length must be >= 0";  // :1634
+      err = "collision: longest_valid_segment_length must be >= 0";  // :1634
       return TMX_ERR_INVALID;
     }
     const int kmax = tm.max_substates < 2 ? 2 : tm.max_substates;
@@ -392,26 +346,26 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
     // index refers to), so terms with different max_substates coexist
     if (kmax > 0x7FFF)
     {
-      ctx->err = "collision: max_substates too large";
+      err = "collision: max_substates too large";
       return TMX_ERR_UNSUPPORTED;
     }
-    lvs_kmax = std::max(lvs_kmax, kmax);
+    L.lvs_kmax = std::max(L.lvs_kmax, kmax);
     const bool cast = tm.evaluator_type != 2, is_cnt_c = tm.kind == TMX_TERM_COLLISION_CNT;
     for (int i = tm.first_step; i < tm.last_step; ++i)
     {
       const bool cur = std::find(tm.fixed_steps, tm.fixed_steps + tm.n_fixed_steps, i) != tm.fixed_steps + tm.n_fixed_steps;
       const bool nxt = std::find(tm.fixed_steps, tm.fixed_steps + tm.n_fixed_steps, i + 1) != tm.fixed_steps + tm.n_fixed_steps;
       const int fl = (cur ? 1 : 0) | ((!cur && nxt) ? 2 : 0) | (cast ? 4 : 0);
-      const int own = is_cnt_c ? n_cnts++ : n_costs++;
+      const int own = is_cnt_c ? L.n_cnts++ : L.n_costs++;
       const int nsub = cast ? kmax - 1 : kmax;
       for (int sp = 0; sp < d->n_link_spheres; ++sp)
         for (int o = 0; o < d->n_obstacles; ++o)
           for (int q = 0; q < nsub; ++q)
           {
             add_slot(SLOT_COLLISION_LVS, i, sp, o, own, 1, is_cnt_c ? 1 : 0, 0, tm.coeff, is_cnt_c ? tm.coeff : 1.0, tm.margin, tm.buffer);
-            c2.back() = R2++;
-            sub3.back() = fl | (q << 3) | (kmax << 16);
-            aux3.back() = tm.longest_valid_segment_length;
+            L.c2.back() = L.R2++;
+            L.sub3.back() = fl | (q << 3) | (kmax << 16);
+            L.aux3.back() = tm.longest_valid_segment_length;
           }
     }
     return TMX_OK;
@@ -420,24 +374,24 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
   const int flavor = d->flavor;
   if (flavor != TMX_FLAVOR_SCO && flavor != TMX_FLAVOR_SQP)
   {
-    ctx->err = "tmx_problem_desc.flavor must be TMX_FLAVOR_SCO or TMX_FLAVOR_SQP";
+    err = "tmx_problem_desc.flavor must be TMX_FLAVOR_SCO or TMX_FLAVOR_SQP";
     return TMX_ERR_INVALID;
   }
   if (flavor == TMX_FLAVOR_SQP && (d->n_fixed_steps > 0 || d->n_fixed_dofs > 0))
   {
-    ctx->err = "TMX_FLAVOR_SQP: fixed_steps / fixed_dofs are not part of the trajopt_sqp path (use JointPos constraint sets)";
+    err = "TMX_FLAVOR_SQP: fixed_steps / fixed_dofs are not part of the trajopt_sqp path (use JointPos constraint sets)";
     return TMX_ERR_UNSUPPORTED;
   }
 #if !TMX_LINK_ROWS
   if (flavor == TMX_FLAVOR_SQP)
   {
-    ctx->err = "TMX_FLAVOR_SQP needs a build with pair rows";
+    err = "TMX_FLAVOR_SQP needs a build with pair rows";
     return TMX_ERR_UNSUPPORTED;
   }
 #endif
   if (flavor == TMX_FLAVOR_SQP && d->use_time)
   {
-    ctx->err = "TMX_FLAVOR_SQP: time-parameterised problems are not part of the trajopt_sqp path (trajopt_ifopt has no such sets)";
+    err = "TMX_FLAVOR_SQP: time-parameterised problems are not part of the trajopt_sqp path (trajopt_ifopt has no such sets)";
     return TMX_ERR_UNSUPPORTED;
   }
   P.flavor = flavor;
@@ -446,7 +400,7 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
   {
     if (t < 0 || t >= T)
     {
-      ctx->err = "fixed timestep out of range";
+      err = "fixed timestep out of range";
       return TMX_ERR_INVALID;
     }
     for (int j = 0; j < DK; ++j)  // (the joint columns only, problem_description.cpp:499-503)
@@ -459,37 +413,17 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
     const int dof = d->fixed_dofs[q];
     if (dof < 0 || dof >= DK)
     {
-      ctx->err = "DOF(aka Joint) indice is greater than the number of DOF available.";
+      err = "DOF(aka Joint) indice is greater than the number of DOF available.";
       return TMX_ERR_INVALID;
     }
     for (int i = 0; i < T; ++i)
       if (std::find(fixed.begin(), fixed.end(), i) == fixed.end())
         add_slot(SLOT_FIXED, i, dof, 0, -1, 0, 0, 1, 0.0, 1.0, 0.0, 0.0);
   }
-  std::vector<double> pd(P.NX, 0.0), po(P.NX, 0.0), pq(P.NX, 0.0), po2(P.NX, 0.0), po3(P.NX, 0.0);
-  std::vector<int> fx_t, fx_kind, fx_owner, fx_op0, fx_nops, fx_c0, fx_nout, fx_slot0, fx_ci, fx_ops;  // function-term instances
-  std::vector<double> fx_consts;
-  int n_fx_cost = 0;
-  int n_stencil = 0;      // rows of difference order 2 / 3
-  bool qp_dense = false;  // time-squared costs, difference rows next to general pair rows: dense QP engine
-  bool tt_terms = false;  // TotalTime terms: dense engine, or - above its size limit - rank-one terms on the block chain
-  bool tt_chain = false;
-  bool tv_terms = false;  // squared JointVel-with-time costs: dense engine, or - above its size limit - joint - time entries on the dense-coupling block chain
-  bool tv_chain = false;
-  std::string tv_why;     // what keeps such costs on the dense engine (text of the refusal above its size limit)
-  bool dyn_p = false;     // function COSTS (CostFromFunc / squared CostFromErrFunc): dynamic D x D objective blocks on the structured solver (round 5)
-  bool stencil_rows = false;  // difference rows of order 2 / 3 (JointAcc / JointJerk Ineq costs, Eq / Ineq constraints)
-  int max_row_order = 0;
-  bool st_terms = false;  // function terms (any): the ST instantiations of the term code, piecewise driver
-  int band = 0;           // acceleration (2) / jerk (3) squared costs: banded objective
-  std::vector<int> vel_first, vel_last, vel_cost, vel_kind, cp_t, cp_owner, cp_iscnt, cp_nrows, cp_idx, cp_slot0;
-  std::vector<double> vel_coeffs, vel_targets, cp_coeff, cp_target;
+  for (std::vector<double>* v : { &L.pd, &L.po, &L.pq, &L.po2, &L.po3 })
+    v->assign(P.NX, 0.0);
   // hatch order: all costs in list order, then the constraints; sco::OptProb keeps equality constraints in front of the
   // inequality constraints (modeling.cpp:234-241), which fixes both the row / aux order and the constraint numbering
-  int n_sq = 0;
-  // time-parameterised terms
-  std::vector<int> tv_owner, tv_joint, tv_first, tv_last, tt_owner, tt_form, tt_slot;
-  std::vector<double> tv_coeff, tv_target, tv_up, tv_lo, tt_coeff, tt_limit;
   auto time_zero_tols = [](const tmx_term& tm, int nj) {
     bool z = true;
     for (int j = 0; j < nj; ++j)
@@ -534,7 +468,7 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
           case TMX_TERM_CART_POSE:  // trajopt_ifopt::CartPosConstraint as a (static) constraint set, round 5
             if (!tm.is_constraint)
             {
-              ctx->err = "TMX_FLAVOR_SQP: cart_pose is lowered as a constraint set (CartPosConstraint) only";
+              err = "TMX_FLAVOR_SQP: cart_pose is lowered as a constraint set (CartPosConstraint) only";
               return TMX_ERR_UNSUPPORTED;
             }
             want = 3;
@@ -543,14 +477,14 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
             want = 4;
             break;
           default:
-            ctx->err = "TMX_FLAVOR_SQP: this term kind is not lowered for the trajopt_sqp flavour (lowered: JointPosConstraint as constraint / "
+            err = "TMX_FLAVOR_SQP: this term kind is not lowered for the trajopt_sqp flavour (lowered: JointPosConstraint as constraint / "
                        "absolute cost, JointVel / JointAccel / JointJerk constraint sets as squared costs, CartPosConstraint as constraint, the "
                        "segment collision sets as hinge cost / constraint); not part of the trajopt_sqp path as built here";
             return TMX_ERR_UNSUPPORTED;
         }
         if ((tm.kind == TMX_TERM_COLLISION_COST || tm.kind == TMX_TERM_COLLISION_CNT) && tm.evaluator_type < 2)
         {
-          ctx->err = "TMX_FLAVOR_SQP lowers the segment collision evaluators (evaluator_type 2..4) only";
+          err = "TMX_FLAVOR_SQP lowers the segment collision evaluators (evaluator_type 2..4) only";
           return TMX_ERR_UNSUPPORTED;
         }
       }
@@ -558,20 +492,20 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
         continue;
       if (tm.kind != TMX_TERM_TOTAL_TIME && (tm.first_step < 0 || tm.last_step >= T || tm.first_step > tm.last_step))
       {
-        ctx->err = "term step range invalid";
+        err = "term step range invalid";
         return TMX_ERR_INVALID;
       }
       if (tm.n_fixed_steps < 0 || (tm.n_fixed_steps > 0 && tm.fixed_steps == nullptr) ||
           (tm.n_fixed_steps > 0 && tm.kind != TMX_TERM_COLLISION_COST && tm.kind != TMX_TERM_COLLISION_CNT && tm.kind != TMX_TERM_FUNC_COST &&
            tm.kind != TMX_TERM_FUNC_CNT && tm.kind != TMX_TERM_FUNC_ERR_COST))
       {
-        ctx->err = "tmx_term.fixed_steps: only collision and function terms carry fixed steps";
+        err = "tmx_term.fixed_steps: only collision and function terms carry fixed steps";
         return TMX_ERR_INVALID;
       }
       for (int q = 0; q < tm.n_fixed_steps; ++q)
         if (tm.fixed_steps[q] < tm.first_step || tm.fixed_steps[q] > tm.last_step)
         {
-          ctx->err = "Fixed step is not between first step and last step";  // problem_description.cpp:1641-1649
+          err = "Fixed step is not between first step and last step";  // problem_description.cpp:1641-1649
           return TMX_ERR_INVALID;
         }
       // CartPose / DynamicCartPose with a tolerance band (CartPoseErrCalculator, kinematic_terms.cpp:206-247: toleranced unless the
@@ -582,7 +516,7 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
         {
           if (tm.lower_tols[i] > tm.upper_tols[i])
           {
-            ctx->err = "CartPoseErrCalculator: Inverted tolerance band - lower > upper at one or more indices";  // kinematic_terms.cpp:47-54
+            err = "CartPoseErrCalculator: Inverted tolerance band - lower > upper at one or more indices";  // kinematic_terms.cpp:47-54
             return TMX_ERR_INVALID;
           }
           pose_tol = pose_tol || std::fabs(tm.lower_tols[i] - tm.upper_tols[i]) > 1e-6;
@@ -594,28 +528,28 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
         {
           if (tm.last_step - 1 - tm.first_step < 0)
           {
-            ctx->err = "JointVelEqCost, trajectory is too short!";  // trajectory_costs.cpp:269-270
+            err = "JointVelEqCost, trajectory is too short!";  // trajectory_costs.cpp:269-270
             return TMX_ERR_INVALID;
           }
-          vel_first.push_back(tm.first_step);
-          vel_last.push_back(tm.last_step);
-          vel_kind.push_back(0);
-          vel_cost.push_back(n_costs++);
+          L.vel_first.push_back(tm.first_step);
+          L.vel_last.push_back(tm.last_step);
+          L.vel_kind.push_back(0);
+          L.vel_cost.push_back(L.n_costs++);
           for (int j = 0; j < TMX_MAX_DOF; ++j)
           {
-            vel_coeffs.push_back(j < DK ? tm.coeffs[j] : 0.0);
-            vel_targets.push_back(j < DK ? tm.targets[j] : 0.0);
+            L.vel_coeffs.push_back(j < DK ? tm.coeffs[j] : 0.0);
+            L.vel_targets.push_back(j < DK ? tm.targets[j] : 0.0);
           }
           if (flavor == TMX_FLAVOR_SQP)
           {
             // JointVelConstraint as a kSquared cost set: H = Bw' Bw with Bw = diag(sqrt(w)) B, B rows (-1 at x[i][j], +1 at
             // x[i+1][j]) accumulated over the rows in row order (AffExprs::square, expressions.cpp:43-112); the 1e-7 zeroing and
             // the factor 2 of OSQPEigenSolver::updateHessianMatrix are applied after all sets are summed (below)
-            ++n_sq;
+            ++L.n_sq;
             for (int j = 0; j < DK; ++j)
               if (!(tm.coeffs[j] > 0))
               {
-                ctx->err = "JointVelConstraint, coeff must be greater than zero.";  // joint_velocity_constraint.cpp:66
+                err = "JointVelConstraint, coeff must be greater than zero.";  // joint_velocity_constraint.cpp:66
                 return TMX_ERR_INVALID;
               }
             for (int i = tm.first_step; i <= tm.last_step - 1; ++i)
@@ -623,9 +557,9 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
               {
                 const double sw = std::sqrt(tm.coeffs[j]);
                 const double b0 = -1 * sw, b1 = 1 * sw;
-                pd[i * D + j] += b0 * b0;
-                po[i * D + j] += b0 * b1;
-                pd[(i + 1) * D + j] += b1 * b1;
+                L.pd[i * D + j] += b0 * b0;
+                L.po[i * D + j] += b0 * b1;
+                L.pd[(i + 1) * D + j] += b1 * b1;
               }
             break;
           }
@@ -638,16 +572,16 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
               const double a0 = -1.0, a1 = 1.0, cst = 0.0 - tm.targets[j];
               const double q00 = (a0 * a0) * c, q01 = (2 * a0 * a1) * c, q11 = (a1 * a1) * c;
               if (q00 != 0.0)
-                pd[i * D + j] += 2.0 * q00;
+                L.pd[i * D + j] += 2.0 * q00;
               if (q11 != 0.0)
-                pd[(i + 1) * D + j] += 2.0 * q11;
+                L.pd[(i + 1) * D + j] += 2.0 * q11;
               if (q01 != 0.0)
-                po[i * D + j] += q01;
+                L.po[i * D + j] += q01;
               const double l0 = (2 * cst * a0) * c, l1 = (2 * cst * a1) * c;
               if (l0 != 0.0)
-                pq[i * D + j] += l0;
+                L.pq[i * D + j] += l0;
               if (l1 != 0.0)
-                pq[(i + 1) * D + j] += l1;
+                L.pq[(i + 1) * D + j] += l1;
             }
           break;
         }
@@ -659,12 +593,12 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
             // bounds; the coefficient weighs the slack pair in the objective (trajopt_qp_problem.cpp:799-812)
             for (int i = tm.first_step; i <= tm.last_step; ++i)
             {
-              const int own = n_cnts++;
+              const int own = L.n_cnts++;
               for (int j = 0; j < DK; ++j)
               {
                 if (!(tm.coeffs[j] > 0))
                 {
-                  ctx->err = "JointPosConstraint, coeff must be greater than zero.";
+                  err = "JointPosConstraint, coeff must be greater than zero.";
                   return TMX_ERR_INVALID;
                 }
                 add_slot(SLOT_JOINTPOS, i, j, 0, own, 2, 1, 1, 0.0, tm.coeffs[j], tm.targets[j], 0.0);
@@ -672,7 +606,7 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
             }
             break;
           }
-          const int own = n_cnts++;
+          const int own = L.n_cnts++;
           for (int i = tm.first_step; i <= tm.last_step; ++i)
             for (int j = 0; j < DK; ++j)
               add_slot(SLOT_JOINTPOS, i, j, 0, own, 2, 1, 1, 0.0, tm.coeffs[j], tm.targets[j], 0.0);
@@ -683,18 +617,18 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
         case TMX_TERM_JOINT_VEL_INEQ_CNT:
         {
 #if !TMX_LINK_ROWS
-          ctx->err = "rows on two consecutive waypoints (JointVel constraint / hinge forms) are not enabled in this build";
+          err = "rows on two consecutive waypoints (JointVel constraint / hinge forms) are not enabled in this build";
           return TMX_ERR_UNSUPPORTED;
 #else
           if (tm.last_step - 1 - tm.first_step < 0)
           {
-            ctx->err = "JointVel term, trajectory is too short!";  // trajectory_costs.cpp:320, :390, :444
+            err = "JointVel term, trajectory is too short!";  // trajectory_costs.cpp:320, :390, :444
             return TMX_ERR_INVALID;
           }
           // one row (EQ) or an upper and a lower row (INEQ) per step i in [first, last - 1] and joint j, in the order of the
           // reference's expr_vec_ (trajectory_costs.cpp:322-346, 392-400, 446-470): home coefficient on x[i][j], link on x[i+1][j]
           const bool is_cnt = tm.kind != TMX_TERM_JOINT_VEL_INEQ_COST;
-          const int own = is_cnt ? n_cnts++ : n_costs++;
+          const int own = is_cnt ? L.n_cnts++ : L.n_costs++;
           for (int i = tm.first_step; i <= tm.last_step - 1; ++i)
             for (int j = 0; j < DK; ++j)
             {
@@ -702,14 +636,14 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
               if (tm.kind == TMX_TERM_JOINT_VEL_EQ_CNT)
               {
                 add_slot(SLOT_JOINTVEL, i, j, 0, own, 2, 1, 1, 0.0, c, tm.targets[j], 0.0);
-                c2.back() = R2++;
+                L.c2.back() = L.R2++;
               }
               else
               {
                 add_slot(SLOT_JOINTVEL_INEQ, i, j, 0, own, 1, is_cnt ? 1 : 0, 0, is_cnt ? 0.0 : 1.0, c, tm.targets[j], tm.upper_tols[j]);
-                c2.back() = R2++;
+                L.c2.back() = L.R2++;
                 add_slot(SLOT_JOINTVEL_INEQ, i, j, 1, own, 1, is_cnt ? 1 : 0, 0, is_cnt ? 0.0 : 1.0, c, tm.targets[j], tm.lower_tols[j]);
-                c2.back() = R2++;
+                L.c2.back() = L.R2++;
               }
             }
           break;
@@ -729,7 +663,7 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
           const bool builtin = tm.kind == TMX_TERM_AVOID_SINGULARITY || pose;
           if (flavor == TMX_FLAVOR_SQP)
           {
-            ctx->err = "TMX_FLAVOR_SQP: function terms are not part of the trajopt_sqp path";
+            err = "TMX_FLAVOR_SQP: function terms are not part of the trajopt_sqp path";
             return TMX_ERR_UNSUPPORTED;
           }
           // (time-parameterised problems: user-defined functions see the joint columns of their waypoint, prob.GetVarRow(s, 0, n_dof) -
@@ -737,12 +671,12 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
           //  for the FK, a zero Jacobian column, and no column of the Jacobian AvoidSingularity decomposes - tmx_terms.h)
           if (!builtin && tmx_expr_check(tm.expr, DK) != 0)
           {
-            ctx->err = "function term: malformed tmx_expr program (opcode, index, stack discipline or outputs)";
+            err = "function term: malformed tmx_expr program (opcode, index, stack discipline or outputs)";
             return TMX_ERR_INVALID;
           }
           if (builtin && tm.kind != TMX_TERM_CART_POSE && (tm.link < 0 || tm.link >= DK))
           {
-            ctx->err = "AvoidSingularity / DynamicCartPose: link is the index of a moving link, 0 .. n_dof - 1";
+            err = "AvoidSingularity / DynamicCartPose: link is the index of a moving link, 0 .. n_dof - 1";
             return TMX_ERR_INVALID;
           }
           const bool is_cnt = builtin ? tm.is_constraint != 0 : tm.kind == TMX_TERM_FUNC_CNT;
@@ -770,74 +704,74 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
               }
           if (tm.kind == TMX_TERM_FUNC_COST && n_out != 1)
           {
-            ctx->err = "TMX_TERM_FUNC_COST: the program of a cost has one output";
+            err = "TMX_TERM_FUNC_COST: the program of a cost has one output";
             return TMX_ERR_INVALID;
           }
           if (is_cnt && cnt_type != 0 && cnt_type != 1)
           {
-            ctx->err = "TMX_TERM_FUNC_CNT: cnt_type must be 0 (EQ) or 1 (INEQ)";
+            err = "TMX_TERM_FUNC_CNT: cnt_type must be 0 (EQ) or 1 (INEQ)";
             return TMX_ERR_INVALID;
           }
           if (tm.kind == TMX_TERM_FUNC_ERR_COST && (penalty_type < 0 || penalty_type > 2))
           {
-            ctx->err = "TMX_TERM_FUNC_ERR_COST: penalty_type must be 0 (SQUARED), 1 (ABS) or 2 (HINGE)";
+            err = "TMX_TERM_FUNC_ERR_COST: penalty_type must be 0 (SQUARED), 1 (ABS) or 2 (HINGE)";
             return TMX_ERR_INVALID;
           }
           // instance kind: 0 / 1 CostFromFunc (diagonal / full Hessian), 2 constraint rows, 3 squared error cost, 4 abs / hinge cost rows
           const int fk = tm.kind == TMX_TERM_FUNC_COST ? (tm.full_hessian ? 1 : 0) : (is_cnt ? 2 : (penalty_type == 0 ? 3 : 4));
           const bool quad = fk == 0 || fk == 1 || fk == 3;
-          st_terms = true;
+          L.st_terms = true;
           if (quad)
-            dyn_p = true;  // P changes with the iterate, but only inside the waypoint's diagonal block: QpWs::pb (row-only function terms leave the QP as it is)
+            L.dyn_p = true;  // P changes with the iterate, but only inside the waypoint's diagonal block: QpWs::pb (row-only function terms leave the QP as it is)
           // the row weights (coeffs, 1 when absent) sit in front of the program's constants
           for (int i = 0; i < TMX_EXPR_MAX_OUT; ++i)
-            fx_consts.push_back(weights[i]);
-          int op0 = (int)fx_ops.size() / 2, n_ops = 0;
-          const int c0 = (int)fx_consts.size();
+            L.fx_consts.push_back(weights[i]);
+          int op0 = (int)L.fx_ops.size() / 2, n_ops = 0;
+          const int c0 = (int)L.fx_consts.size();
           if (!builtin)
           {
             n_ops = tm.expr->n_ops;
-            fx_ops.insert(fx_ops.end(), tm.expr->ops, tm.expr->ops + 2 * tm.expr->n_ops);
-            fx_consts.insert(fx_consts.end(), tm.expr->consts, tm.expr->consts + tm.expr->n_consts);
+            L.fx_ops.insert(L.fx_ops.end(), tm.expr->ops, tm.expr->ops + 2 * tm.expr->n_ops);
+            L.fx_consts.insert(L.fx_consts.end(), tm.expr->consts, tm.expr->consts + tm.expr->n_consts);
           }
           else if (tm.kind == TMX_TERM_AVOID_SINGULARITY)
           {
             if (tm.subset_first < 0 || tm.subset_first > tm.link + 1)
             {
-              ctx->err = "AvoidSingularity: subset_first is 0 (all joints) or 1 + the first joint of a subset that ends at `link`";
+              err = "AvoidSingularity: subset_first is 0 (all joints) or 1 + the first joint of a subset that ends at `link`";
               return TMX_ERR_INVALID;
             }
             op0 = tm.link;
             n_ops = -1;
-            fx_consts.push_back(tm.lambda);
-            fx_consts.push_back((double)tm.subset_first);
+            L.fx_consts.push_back(tm.lambda);
+            L.fx_consts.push_back((double)tm.subset_first);
           }
           else
           {
             op0 = tm.kind == TMX_TERM_CART_POSE ? -1 : tm.link;  // -1: the frame is world_T_target itself
             n_ops = -2;
-            fx_consts.insert(fx_consts.end(), tm.target_pose, tm.target_pose + 12);  // link_T_target (world_T_target)
+            L.fx_consts.insert(L.fx_consts.end(), tm.target_pose, tm.target_pose + 12);  // link_T_target (world_T_target)
             for (int i = 0; i < 6; ++i)
-              fx_consts.push_back((double)pose_idx[i]);
-            fx_consts.push_back(pose_tol ? 1.0 : 0.0);
-            fx_consts.insert(fx_consts.end(), tm.lower_tols, tm.lower_tols + 6);
-            fx_consts.insert(fx_consts.end(), tm.upper_tols, tm.upper_tols + 6);
+              L.fx_consts.push_back((double)pose_idx[i]);
+            L.fx_consts.push_back(pose_tol ? 1.0 : 0.0);
+            L.fx_consts.insert(L.fx_consts.end(), tm.lower_tols, tm.lower_tols + 6);
+            L.fx_consts.insert(L.fx_consts.end(), tm.upper_tols, tm.upper_tols + 6);
           }
           for (int t = tm.first_step; t <= tm.last_step; ++t)
           {
             if (!builtin && std::find(tm.fixed_steps, tm.fixed_steps + tm.n_fixed_steps, t) != tm.fixed_steps + tm.n_fixed_steps)
               continue;  // UserDefinedTermInfo::fixed_steps (problem_description.cpp:608, :645)
-            const int inst = (int)fx_t.size();
-            const int own = is_cnt ? n_cnts++ : n_costs++;
-            fx_t.push_back(t);
-            fx_kind.push_back(fk);
-            fx_owner.push_back(own);
-            fx_op0.push_back(op0);
-            fx_nops.push_back(n_ops);
-            fx_c0.push_back(c0);
-            fx_nout.push_back(n_out);
-            fx_slot0.push_back((int)kind.size());
-            fx_ci.push_back(quad ? n_fx_cost++ : -1);
+            const int inst = (int)L.fx_t.size();
+            const int own = is_cnt ? L.n_cnts++ : L.n_costs++;
+            L.fx_t.push_back(t);
+            L.fx_kind.push_back(fk);
+            L.fx_owner.push_back(own);
+            L.fx_op0.push_back(op0);
+            L.fx_nops.push_back(n_ops);
+            L.fx_c0.push_back(c0);
+            L.fx_nout.push_back(n_out);
+            L.fx_slot0.push_back((int)L.kind.size());
+            L.fx_ci.push_back(quad ? L.n_fx_cost++ : -1);
             if (!quad)
               for (int i = 0; i < n_out; ++i)
               {
@@ -861,7 +795,7 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
           const int ord = tm.kind == TMX_TERM_JOINT_ACC_EQ_COST ? 2 : 3;
           if (!TMX_LINK_ROWS)
           {
-            ctx->err = "rows on several waypoints (joint acceleration / jerk terms) are not enabled in this build";
+            err = "rows on several waypoints (joint acceleration / jerk terms) are not enabled in this build";
             return TMX_ERR_UNSUPPORTED;
           }
           if (flavor == TMX_FLAVOR_SQP)
@@ -874,27 +808,27 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
             const int n = tm.last_step - tm.first_step + 1;
             if (n < (ord == 2 ? 4 : 6))
             {
-              ctx->err = ord == 2 ? "JointAccelConstraint requires a minimum of four position variables!"   // joint_acceleration_constraint.cpp:45-46
+              err = ord == 2 ? "JointAccelConstraint requires a minimum of four position variables!"   // joint_acceleration_constraint.cpp:45-46
                                   : "JointJerkConstraint requires a minimum of six position variables!";    // joint_jerk_constraint.cpp:45-46
               return TMX_ERR_INVALID;
             }
             for (int j = 0; j < DK; ++j)
               if (!(tm.coeffs[j] > 0))
               {
-                ctx->err = ord == 2 ? "JointAccelConstraint, coeff must be greater than zero." : "JointJerkConstraint, coeff must be greater than zero.";
+                err = ord == 2 ? "JointAccelConstraint, coeff must be greater than zero." : "JointJerkConstraint, coeff must be greater than zero.";
                 return TMX_ERR_INVALID;
               }
-            ++n_sq;
-            band = std::max(band, ord);
-            st_terms = true;  // (the squared-set code of these kinds is instantiated in the piecewise kernels)
-            vel_first.push_back(tm.first_step);
-            vel_last.push_back(tm.last_step);
-            vel_kind.push_back(ord + 2);  // 4: ifopt accel, 5: ifopt jerk (tmx_terms.h: vel_is_ifopt_kind)
-            vel_cost.push_back(n_costs++);
+            ++L.n_sq;
+            L.band = std::max(L.band, ord);
+            L.st_terms = true;  // (the squared-set code of these kinds is instantiated in the piecewise kernels)
+            L.vel_first.push_back(tm.first_step);
+            L.vel_last.push_back(tm.last_step);
+            L.vel_kind.push_back(ord + 2);  // 4: ifopt accel, 5: ifopt jerk (tmx_terms.h: vel_is_ifopt_kind)
+            L.vel_cost.push_back(L.n_costs++);
             for (int j = 0; j < TMX_MAX_DOF; ++j)
             {
-              vel_coeffs.push_back(j < DK ? tm.coeffs[j] : 0.0);
-              vel_targets.push_back(j < DK ? tm.targets[j] : 0.0);
+              L.vel_coeffs.push_back(j < DK ? tm.coeffs[j] : 0.0);
+              L.vel_targets.push_back(j < DK ? tm.targets[j] : 0.0);
             }
             static const double E2[3] = { 1.0, -2.0, 1.0 }, E3[4] = { -1.0, 3.0, -3.0, 1.0 };
             const double* e = ord == 2 ? E2 : E3;
@@ -907,10 +841,10 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
                 for (int k = 0; k <= ord; ++k)
                 {
                   const double bk = e[k] * sw;
-                  pd[(a0 + k) * D + j] += bk * bk;
+                  L.pd[(a0 + k) * D + j] += bk * bk;
                   for (int l = k + 1; l <= ord; ++l)
                   {
-                    std::vector<double>& bnd = (l - k == 1) ? po : ((l - k == 2) ? po2 : po3);
+                    std::vector<double>& bnd = (l - k == 1) ? L.po : ((l - k == 2) ? L.po2 : L.po3);
                     bnd[(a0 + k) * D + j] += bk * (e[l] * sw);
                   }
                 }
@@ -920,18 +854,18 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
           }
           if (tm.last_step - ord - tm.first_step < 0)
           {
-            ctx->err = ord == 2 ? "JointAccEqCost, trajectory is too short!" : "JointJerkEqCost, trajectory is too short!";  // :515, :768
+            err = ord == 2 ? "JointAccEqCost, trajectory is too short!" : "JointJerkEqCost, trajectory is too short!";  // :515, :768
             return TMX_ERR_INVALID;
           }
-          band = std::max(band, ord);
-          vel_first.push_back(tm.first_step);
-          vel_last.push_back(tm.last_step);
-          vel_kind.push_back(ord);
-          vel_cost.push_back(n_costs++);
+          L.band = std::max(L.band, ord);
+          L.vel_first.push_back(tm.first_step);
+          L.vel_last.push_back(tm.last_step);
+          L.vel_kind.push_back(ord);
+          L.vel_cost.push_back(L.n_costs++);
           for (int j = 0; j < TMX_MAX_DOF; ++j)
           {
-            vel_coeffs.push_back(j < DK ? tm.coeffs[j] : 0.0);
-            vel_targets.push_back(j < DK ? tm.targets[j] : 0.0);
+            L.vel_coeffs.push_back(j < DK ? tm.coeffs[j] : 0.0);
+            L.vel_targets.push_back(j < DK ? tm.targets[j] : 0.0);
           }
           static const double S2[3] = { 1.0, -2.0, 1.0 }, S3[4] = { -1.0, 3.0, -3.0, 1.0 };
           const double* a = ord == 2 ? S2 : S3;
@@ -943,17 +877,17 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
               {
                 const double qkk = (a[k] * a[k]) * c;
                 if (qkk != 0.0)
-                  pd[(i + k) * D + j] += 2.0 * qkk;
+                  L.pd[(i + k) * D + j] += 2.0 * qkk;
                 const double lk = (2 * cst * a[k]) * c;
                 if (lk != 0.0)
-                  pq[(i + k) * D + j] += lk;
+                  L.pq[(i + k) * D + j] += lk;
                 for (int l = k + 1; l <= ord; ++l)
                 {
                   const double qkl = (2 * a[k] * a[l]) * c;
                   if (qkl == 0.0)
                     continue;
-                  std::vector<double>& band = (l - k == 1) ? po : ((l - k == 2) ? po2 : po3);
-                  band[(i + k) * D + j] += qkl;
+                  std::vector<double>& bnd = (l - k == 1) ? L.po : ((l - k == 2) ? L.po2 : L.po3);
+                  bnd[(i + k) * D + j] += qkl;
                 }
               }
             }
@@ -967,7 +901,7 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
         case TMX_TERM_JOINT_JERK_INEQ_CNT:
         {
 #if !TMX_LINK_ROWS
-          ctx->err = "rows on several waypoints (joint acceleration / jerk terms) are not enabled in this build";
+          err = "rows on several waypoints (joint acceleration / jerk terms) are not enabled in this build";
           return TMX_ERR_UNSUPPORTED;
 #else
           const bool acc = tm.kind == TMX_TERM_JOINT_ACC_EQ_CNT || tm.kind == TMX_TERM_JOINT_ACC_INEQ_COST || tm.kind == TMX_TERM_JOINT_ACC_INEQ_CNT;
@@ -976,20 +910,20 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
           const bool is_cost = tm.kind == TMX_TERM_JOINT_ACC_INEQ_COST || tm.kind == TMX_TERM_JOINT_JERK_INEQ_COST;
           if (flavor == TMX_FLAVOR_SQP)
           {
-            ctx->err = "TMX_FLAVOR_SQP: the ROW forms of the joint acceleration / jerk terms are not lowered for the trajopt_sqp flavour (their "
+            err = "TMX_FLAVOR_SQP: the ROW forms of the joint acceleration / jerk terms are not lowered for the trajopt_sqp flavour (their "
                        "squared cost sets are); not part of the trajopt_sqp path as built here";
             return TMX_ERR_UNSUPPORTED;
           }
           if (tm.last_step - ord - tm.first_step < 0)
           {
-            ctx->err = acc ? "JointAcc term, trajectory is too short!" : "JointJerk term, trajectory is too short!";  // :575, :642, :699, ...
+            err = acc ? "JointAcc term, trajectory is too short!" : "JointJerk term, trajectory is too short!";  // :575, :642, :699, ...
             return TMX_ERR_INVALID;
           }
-          stencil_rows = true;  // (structured banded path or dense engine: decided below, when every term is known)
-          max_row_order = std::max(max_row_order, ord);
+          L.stencil_rows = true;  // (structured banded path or dense engine: decided below, when every term is known)
+          L.max_row_order = std::max(L.max_row_order, ord);
           // rows in the order of the reference's expr_vec_ (:577-601, :644-652, :703-727 and the jerk twins): one row (EQ) or an
           // upper and a lower row (INEQ) per step i in [first, last - ord] and joint j over x[i .. i + ord][j]
-          const int own = is_cost ? n_costs++ : n_cnts++;
+          const int own = is_cost ? L.n_costs++ : L.n_cnts++;
           for (int i = tm.first_step; i <= tm.last_step - ord; ++i)
             for (int j = 0; j < DK; ++j)
             {
@@ -997,19 +931,19 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
               if (is_eq)
               {
                 add_slot(SLOT_JOINTVEL, i, j, 0, own, 2, 1, 1, 0.0, c, tm.targets[j], 0.0);
-                c2.back() = R2++;
-                sub3.back() = ord;
-                ++n_stencil;
+                L.c2.back() = L.R2++;
+                L.sub3.back() = ord;
+                ++L.n_stencil;
               }
               else
               {
                 add_slot(SLOT_JOINTVEL_INEQ, i, j, 0, own, 1, is_cost ? 0 : 1, 0, is_cost ? 1.0 : 0.0, c, tm.targets[j], tm.upper_tols[j]);
-                c2.back() = R2++;
-                sub3.back() = ord;
+                L.c2.back() = L.R2++;
+                L.sub3.back() = ord;
                 add_slot(SLOT_JOINTVEL_INEQ, i, j, 1, own, 1, is_cost ? 0 : 1, 0, is_cost ? 1.0 : 0.0, c, tm.targets[j], tm.lower_tols[j]);
-                c2.back() = R2++;
-                sub3.back() = ord;
-                n_stencil += 2;
+                L.c2.back() = L.R2++;
+                L.sub3.back() = ord;
+                L.n_stencil += 2;
               }
             }
           break;
@@ -1022,12 +956,12 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
             // JointPosConstraint per step as a kAbsolute cost set: the same rows, slack pair weighted by the coefficient
             for (int i = tm.first_step; i <= tm.last_step; ++i)
             {
-              const int own = n_costs++;
+              const int own = L.n_costs++;
               for (int j = 0; j < DK; ++j)
               {
                 if (!(tm.coeffs[j] > 0))
                 {
-                  ctx->err = "JointPosConstraint, coeff must be greater than zero.";
+                  err = "JointPosConstraint, coeff must be greater than zero.";
                   return TMX_ERR_INVALID;
                 }
                 add_slot(SLOT_JOINTPOS, i, j, 0, own, 2, 0, 1, tm.coeffs[j], tm.coeffs[j], tm.targets[j], 0.0);
@@ -1037,14 +971,14 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
           }
           // JointPosEqCost (trajectory_costs.cpp:28-65): squared cost on the joint positions; shares the device-side
           // machinery of the velocity cost (vel_kind 1: the term is x_ij - target_j instead of a difference of steps)
-          vel_first.push_back(tm.first_step);
-          vel_last.push_back(tm.last_step);
-          vel_kind.push_back(1);
-          vel_cost.push_back(n_costs++);
+          L.vel_first.push_back(tm.first_step);
+          L.vel_last.push_back(tm.last_step);
+          L.vel_kind.push_back(1);
+          L.vel_cost.push_back(L.n_costs++);
           for (int j = 0; j < TMX_MAX_DOF; ++j)
           {
-            vel_coeffs.push_back(j < DK ? tm.coeffs[j] : 0.0);
-            vel_targets.push_back(j < DK ? tm.targets[j] : 0.0);
+            L.vel_coeffs.push_back(j < DK ? tm.coeffs[j] : 0.0);
+            L.vel_targets.push_back(j < DK ? tm.targets[j] : 0.0);
           }
           // exprSquare(pos) * coeff with pos = 1*x - target  ->  Hessian 2*c on the diagonal, linear term 2*(0 - target)*c
           for (int i = tm.first_step; i <= tm.last_step; ++i)
@@ -1054,10 +988,10 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
               const double a1 = 1.0, cst = 0.0 - tm.targets[j];
               const double q11 = (a1 * a1) * c;
               if (q11 != 0.0)
-                pd[i * D + j] += 2.0 * q11;
+                L.pd[i * D + j] += 2.0 * q11;
               const double l1 = (2 * cst * a1) * c;
               if (l1 != 0.0)
-                pq[i * D + j] += l1;
+                L.pq[i * D + j] += l1;
             }
           break;
         }
@@ -1065,7 +999,7 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
         {
           // JointPosIneqCost (trajectory_costs.cpp:67-137): the rows of the inequality constraint as hinge costs with
           // objective coefficient 1 (the per-joint coefficient already sits inside the affine expression)
-          const int own = n_costs++;
+          const int own = L.n_costs++;
           for (int i = tm.first_step; i <= tm.last_step; ++i)
             for (int j = 0; j < DK; ++j)
             {
@@ -1078,7 +1012,7 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
         {
           // JointPosIneqConstraint (trajectory_costs.cpp:185-225): per step and joint an upper and a lower row, each an
           // inequality constraint -> hinge penalty (1 aux).  scale = coeff, aux1 = target, aux2 = tolerance
-          const int own = n_cnts++;
+          const int own = L.n_cnts++;
           for (int i = tm.first_step; i <= tm.last_step; ++i)
             for (int j = 0; j < DK; ++j)
             {
@@ -1091,59 +1025,59 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
         {
           for (int t = tm.first_step; t <= tm.last_step; ++t)
           {
-            const int own = tm.is_constraint ? n_cnts++ : n_costs++;
-            const int inst = static_cast<int>(cp_t.size());
-            cp_t.push_back(t);
-            cp_owner.push_back(own);
-            cp_iscnt.push_back(tm.is_constraint ? 1 : 0);
-            cp_slot0.push_back(static_cast<int>(kind.size()));
+            const int own = tm.is_constraint ? L.n_cnts++ : L.n_costs++;
+            const int inst = static_cast<int>(L.cp_t.size());
+            L.cp_t.push_back(t);
+            L.cp_owner.push_back(own);
+            L.cp_iscnt.push_back(tm.is_constraint ? 1 : 0);
+            L.cp_slot0.push_back(static_cast<int>(L.kind.size()));
             int nr = 0;
             for (int i = 0; i < 6; ++i)
             {
               // problem_description.cpp:910-926; trajopt_ifopt::CartPosConstraint drops the rows whose coefficient is
               // almostEqualRelativeAndAbs(c, 0) (cartesian_position_constraint.cpp:95, :121)
               const bool keep = std::fabs(tm.coeffs[i]) > (flavor == TMX_FLAVOR_SQP ? 1e-6 : 1e-5);
-              cp_idx.push_back(0);
-              cp_coeff.push_back(0.0);
+              L.cp_idx.push_back(0);
+              L.cp_coeff.push_back(0.0);
               if (keep)
               {
-                cp_idx[inst * 6 + nr] = i;
-                cp_coeff[inst * 6 + nr] = tm.coeffs[i];
+                L.cp_idx[inst * 6 + nr] = i;
+                L.cp_coeff[inst * 6 + nr] = tm.coeffs[i];
                 add_slot(SLOT_CARTPOSE, t, nr, i, own, 2, tm.is_constraint ? 1 : 0, 1, 1.0, tm.coeffs[i], 0.0, 0.0);
                 ++nr;
               }
             }
-            cp_nrows.push_back(nr);
+            L.cp_nrows.push_back(nr);
             for (int q = 0; q < 12; ++q)
-              cp_target.push_back(tm.target_pose[q]);
+              L.cp_target.push_back(tm.target_pose[q]);
           }
           break;
         }
         case TMX_TERM_CART_VEL:
         {
 #if !TMX_LINK_ROWS
-          ctx->err = "rows on two consecutive waypoints (CartVel) are not enabled in this build";
+          err = "rows on two consecutive waypoints (CartVel) are not enabled in this build";
           return TMX_ERR_UNSUPPORTED;
 #else
           if (tm.last_step + 1 >= T)
           {
-            ctx->err = "cart_vel: last_step + 1 must be a waypoint of the trajectory (the term couples steps i and i + 1)";
+            err = "cart_vel: last_step + 1 must be a waypoint of the trajectory (the term couples steps i and i + 1)";
             return TMX_ERR_INVALID;
           }
           if (flavor == TMX_FLAVOR_SQP)
           {
-            ctx->err = "TMX_FLAVOR_SQP: cart_vel is not part of the trajopt_sqp path";
+            err = "TMX_FLAVOR_SQP: cart_vel is not part of the trajopt_sqp path";
             return TMX_ERR_UNSUPPORTED;
           }
           // CartVelTermInfo::hatch (problem_description.cpp:1011-1057): one cost / constraint per step i in [first, last] over
           // waypoints i and i + 1, six rows each
           for (int t = tm.first_step; t <= tm.last_step; ++t)
           {
-            const int own = tm.is_constraint ? n_cnts++ : n_costs++;
+            const int own = tm.is_constraint ? L.n_cnts++ : L.n_costs++;
             for (int i = 0; i < 6; ++i)
             {
               add_slot(SLOT_CARTVEL, t, i, 0, own, tm.is_constraint ? 1 : 2, tm.is_constraint ? 1 : 0, tm.is_constraint ? 0 : 1, 1.0, 1.0, tm.margin, 0.0);
-              c2.back() = R2++;
+              L.c2.back() = L.R2++;
             }
           }
           break;
@@ -1153,7 +1087,7 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
         {
           if (tm.evaluator_type < 0 || tm.evaluator_type > 4)
           {
-            ctx->err = "collision evaluator_type must be <= 4";  // FAIL_IF_FALSE, problem_description.cpp:1637
+            err = "collision evaluator_type must be <= 4";  // FAIL_IF_FALSE, problem_description.cpp:1637
             return TMX_ERR_INVALID;
           }
           if (tm.evaluator_type >= 2)
@@ -1167,7 +1101,7 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
           {
             if (std::find(tm.fixed_steps, tm.fixed_steps + tm.n_fixed_steps, i) != tm.fixed_steps + tm.n_fixed_steps)
               continue;  // the term's own fixed_steps, problem_description.cpp:1767
-            const int own = n_costs++;
+            const int own = L.n_costs++;
             for (int s = 0; s < d->n_link_spheres; ++s)
               for (int o = 0; o < d->n_obstacles; ++o)
                 add_slot(SLOT_COLLISION, i, s, o, own, 1, 0, 0, tm.coeff, 1.0, tm.margin, tm.buffer);
@@ -1178,7 +1112,7 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
         {
           if (tm.evaluator_type < 0 || tm.evaluator_type > 4)
           {
-            ctx->err = "collision evaluator_type must be <= 4";  // FAIL_IF_FALSE, problem_description.cpp:1637
+            err = "collision evaluator_type must be <= 4";  // FAIL_IF_FALSE, problem_description.cpp:1637
             return TMX_ERR_INVALID;
           }
           if (tm.evaluator_type >= 2)
@@ -1194,7 +1128,7 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
           {
             if (std::find(tm.fixed_steps, tm.fixed_steps + tm.n_fixed_steps, i) != tm.fixed_steps + tm.n_fixed_steps)
               continue;  // :1827
-            const int own = n_cnts++;
+            const int own = L.n_cnts++;
             for (int s = 0; s < d->n_link_spheres; ++s)
               for (int o = 0; o < d->n_obstacles; ++o)
                 add_slot(SLOT_COLLISION, i, s, o, own, 1, 1, 0, tm.coeff, tm.coeff, tm.margin, tm.buffer);
@@ -1207,33 +1141,33 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
           // TrajOptConstraintFromErrFunc over 2 (last - first) rows - the upper rows, then the lower rows - with the coefficient
           // coeffs[j] on every row (a zero coefficient drops the rows, modeling_utils.cpp:175-176, :258-259; the cost stays)
 #if !TMX_LINK_ROWS
-          ctx->err = "rows on two consecutive waypoints (time-parameterised joint velocities) are not enabled in this build";
+          err = "rows on two consecutive waypoints (time-parameterised joint velocities) are not enabled in this build";
           return TMX_ERR_UNSUPPORTED;
 #else
           if (tm.last_step - tm.first_step < 1)
           {
-            ctx->err = "joint_vel with use_time: the term needs two steps";
+            err = "joint_vel with use_time: the term needs two steps";
             return TMX_ERR_INVALID;
           }
           const bool zero = time_zero_tols(tm, DK);
           for (int j = 0; j < DK; ++j)
           {
-            const int own = tm.is_constraint ? n_cnts++ : n_costs++;
+            const int own = tm.is_constraint ? L.n_cnts++ : L.n_costs++;
             const double c = tm.coeffs[j];
             if (!tm.is_constraint && zero)
             {
               // sco::SQUARED: a dynamic quadratic model over (x[i][j], x[i+1][j], tau[i+1]) of every segment
               if (c != 0.0)
               {
-                tv_owner.push_back(own);
-                tv_joint.push_back(j);
-                tv_first.push_back(tm.first_step);
-                tv_last.push_back(tm.last_step);
-                tv_coeff.push_back(c);
-                tv_target.push_back(tm.targets[j]);
-                tv_up.push_back(tm.upper_tols[j]);
-                tv_lo.push_back(tm.lower_tols[j]);
-                tv_terms = true;  // P changes with the iterate and couples a joint with the NEXT waypoint's time variable (engine: decided below)
+                L.tv_owner.push_back(own);
+                L.tv_joint.push_back(j);
+                L.tv_first.push_back(tm.first_step);
+                L.tv_last.push_back(tm.last_step);
+                L.tv_coeff.push_back(c);
+                L.tv_target.push_back(tm.targets[j]);
+                L.tv_up.push_back(tm.upper_tols[j]);
+                L.tv_lo.push_back(tm.lower_tols[j]);
+                L.tv_terms = true;  // P changes with the iterate and couples a joint with the NEXT waypoint's time variable (engine: decided below)
               }
               continue;
             }
@@ -1247,10 +1181,10 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
                   add_slot(SLOT_JOINTVEL_TIME, i, j, half, own, zero ? 2 : 1, 1, zero ? 1 : 0, 0.0, c, tm.targets[j], tol);
                 else                   // sco::HINGE: exprScale(aff, coeff); addHinge(aff, 1)
                   add_slot(SLOT_JOINTVEL_TIME, i, j, half, own, 1, 0, 0, 1.0, c, tm.targets[j], tol);
-                c2.back() = R2++;
+                L.c2.back() = L.R2++;
               }
           }
-          st_terms = true;  // (rows only: the QP stays a block chain with pair rows - structured solvers, piecewise driver)
+          L.st_terms = true;  // (rows only: the QP stays a block chain with pair rows - structured solvers, piecewise driver)
           break;
 #endif
         }
@@ -1259,34 +1193,34 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
           // TotalTimeTermInfo::hatch (problem_description.cpp:1852-1890): one cost / constraint over tau[1 .. T-1]
           if (T < 2)
           {
-            ctx->err = "total_time: the problem needs two steps";
+            err = "total_time: the problem needs two steps";
             return TMX_ERR_INVALID;
           }
           const bool zero = std::fabs(tm.margin) < 1e-5;
-          const int own = tm.is_constraint ? n_cnts++ : n_costs++;
+          const int own = tm.is_constraint ? L.n_cnts++ : L.n_costs++;
           const int form = tm.is_constraint ? (zero ? 2 : 3) : (zero ? 0 : 1);
           int slot = -1;
           if (form != 0 && tm.coeff != 0.0)
           {
-            slot = (int)kind.size();
+            slot = (int)L.kind.size();
             if (form == 1)
-              add_slot(SLOT_TOTAL_TIME, 1, (int)tt_owner.size(), 0, own, 1, 0, 0, 1.0, tm.coeff, 0.0, 0.0);
+              add_slot(SLOT_TOTAL_TIME, 1, (int)L.tt_owner.size(), 0, own, 1, 0, 0, 1.0, tm.coeff, 0.0, 0.0);
             else
-              add_slot(SLOT_TOTAL_TIME, 1, (int)tt_owner.size(), 0, own, form == 2 ? 2 : 1, 1, form == 2 ? 1 : 0, 0.0, tm.coeff, 0.0, 0.0);
+              add_slot(SLOT_TOTAL_TIME, 1, (int)L.tt_owner.size(), 0, own, form == 2 ? 2 : 1, 1, form == 2 ? 1 : 0, 0.0, tm.coeff, 0.0, 0.0);
           }
           if (form == 0 && tm.coeff == 0.0)
             break;  // (no model, the value is zero: nothing to carry)
-          tt_owner.push_back(own);
-          tt_form.push_back(form);
-          tt_slot.push_back(slot);
-          tt_coeff.push_back(tm.coeff);
-          tt_limit.push_back(tm.margin);
-          st_terms = true;
-          tt_terms = true;  // (dense engine or rank-one terms on the block chain: decided below, when every term is known)
+          L.tt_owner.push_back(own);
+          L.tt_form.push_back(form);
+          L.tt_slot.push_back(slot);
+          L.tt_coeff.push_back(tm.coeff);
+          L.tt_limit.push_back(tm.margin);
+          L.st_terms = true;
+          L.tt_terms = true;  // (dense engine or rank-one terms on the block chain: decided below, when every term is known)
           break;
         }
         default:
-          ctx->err = "term kind not lowered by the device path";
+          err = "term kind not lowered by the device path";
           return TMX_ERR_UNSUPPORTED;
       }
     }
@@ -1296,51 +1230,192 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
       // "originally it pruned these but it changes sparsity so we now set to zero" (trajopt_qp_problem.cpp:938-942), then
       // OSQPEigenSolver::updateHessianMatrix: 2 H (osqp_eigen_solver.cpp:220-229).  A zeroed entry stays in the pattern
       // upstream; it does not contribute to any product here.
-      pd[v] = 2.0 * ((std::fabs(pd[v]) < 1e-7) ? 0.0 : pd[v]);
-      po[v] = 2.0 * ((std::fabs(po[v]) < 1e-7) ? 0.0 : po[v]);
-      po2[v] = 2.0 * ((std::fabs(po2[v]) < 1e-7) ? 0.0 : po2[v]);   // (JointAccelConstraint / JointJerkConstraint squared sets)
-      po3[v] = 2.0 * ((std::fabs(po3[v]) < 1e-7) ? 0.0 : po3[v]);
+      L.pd[v] = 2.0 * ((std::fabs(L.pd[v]) < 1e-7) ? 0.0 : L.pd[v]);
+      L.po[v] = 2.0 * ((std::fabs(L.po[v]) < 1e-7) ? 0.0 : L.po[v]);
+      L.po2[v] = 2.0 * ((std::fabs(L.po2[v]) < 1e-7) ? 0.0 : L.po2[v]);   // (JointAccelConstraint / JointJerkConstraint squared sets)
+      L.po3[v] = 2.0 * ((std::fabs(L.po3[v]) < 1e-7) ? 0.0 : L.po3[v]);
     }
-  P.n_sq = n_sq;
-  const int R = static_cast<int>(kind.size());
-  P.R = R;
-  P.n_costs = n_costs;
-  P.n_cnts = n_cnts;
-  P.n_cp = static_cast<int>(cp_t.size());
-  P.n_vel = static_cast<int>(vel_first.size());
-  std::vector<int> aoff(R, 0);
-  int NA = 0;
-  for (int r = 0; r < R; ++r)
+  P.n_sq = L.n_sq;
+  L.R = static_cast<int>(L.kind.size());
+  P.R = L.R;
+  P.n_costs = L.n_costs;
+  P.n_cnts = L.n_cnts;
+  P.n_cp = static_cast<int>(L.cp_t.size());
+  P.n_vel = static_cast<int>(L.vel_first.size());
+  L.aoff.assign(L.R, 0);
+  for (int r = 0; r < L.R; ++r)
   {
-    aoff[r] = NA;
-    NA += naux[r];
+    L.aoff[r] = L.NA;
+    L.NA += L.naux[r];
   }
-  P.NA = NA;
-  P.n_max = P.NX + NA;
-  P.m_max = R + P.NX + NA;
+  P.NA = L.NA;
+  P.n_max = P.NX + L.NA;
+  P.m_max = L.R + P.NX + L.NA;
   int nnzP = 0;
   for (int v = 0; v < P.NX; ++v)
-    nnzP += (pd[v] != 0.0) + (v < P.NX - D && po[v] != 0.0) + (v < P.NX - 2 * D && po2[v] != 0.0) + (v < P.NX - 3 * D && po3[v] != 0.0);
+    nnzP += (L.pd[v] != 0.0) + (v < P.NX - D && L.po[v] != 0.0) + (v < P.NX - 2 * D && L.po2[v] != 0.0) + (v < P.NX - 3 * D && L.po3[v] != 0.0);
   P.nnzP = nnzP;
   // column c of upper-triangular P holds (c-3D, c) / (c-2D, c) if po3 / po2 are set there (jerk / acceleration costs), (c-D, c) if
   // po[c-D] != 0 and (c, c) if pd[c] != 0
-  std::vector<int> p_colptr(P.NX + 1, 0);
+  L.p_colptr.assign(P.NX + 1, 0);
   for (int c = 0; c < P.NX; ++c)
-    p_colptr[c + 1] = p_colptr[c] + ((c >= 3 * D && po3[c - 3 * D] != 0.0) ? 1 : 0) + ((c >= 2 * D && po2[c - 2 * D] != 0.0) ? 1 : 0) +
-                      ((c >= D && po[c - D] != 0.0) ? 1 : 0) + ((pd[c] != 0.0) ? 1 : 0);
+    L.p_colptr[c + 1] = L.p_colptr[c] + ((c >= 3 * D && L.po3[c - 3 * D] != 0.0) ? 1 : 0) + ((c >= 2 * D && L.po2[c - 2 * D] != 0.0) ? 1 : 0) +
+                      ((c >= D && L.po[c - D] != 0.0) ? 1 : 0) + ((L.pd[c] != 0.0) ? 1 : 0);
+  P.n_stencil = L.n_stencil;
+  P.lvs_kmax = L.lvs_kmax;
+  P.n_fx = (int)L.fx_t.size();
+  P.n_fx_cost = L.n_fx_cost;
+  P.n_tv = (int)L.tv_owner.size();
+  P.n_tt = (int)L.tt_owner.size();
+  // slots grouped by waypoint, ascending slot id inside a waypoint
+  L.wp_start.assign(T + 1, 0);
+  L.wp_list.assign(L.R, 0);
+  for (int r = 0; r < L.R; ++r)
+    L.wp_start[L.st[r] + 1]++;
+  for (int t = 0; t < T; ++t)
+    L.wp_start[t + 1] += L.wp_start[t];
+  {
+    std::vector<int> next(L.wp_start.begin(), L.wp_start.end() - 1);
+    for (int r = 0; r < L.R; ++r)
+      L.wp_list[next[L.st[r]]++] = r;
+  }
+  int n_ls_hull = 0;
+  int n_ls_capsule = 0, n_ob_box = 0;
+  for (int s = 0; s < d->n_link_spheres; ++s)
+  {
+    if (d->link_spheres[s].link < 0 || d->link_spheres[s].link >= D)
+    {
+      err = "link sphere attached to an invalid link";
+      return TMX_ERR_INVALID;
+    }
+    L.ls_link.push_back(d->link_spheres[s].link);
+    for (int q = 0; q < 3; ++q)
+      L.ls_center.push_back(d->link_spheres[s].center[q]);
+    L.ls_radius.push_back(d->link_spheres[s].radius);
+    bool cap = false;
+    for (int q = 0; q < 3; ++q)
+    {
+      const double a = d->link_sphere_axes ? d->link_sphere_axes[3 * s + q] : 0.0;
+      L.ls_axis.push_back(a);
+      cap = cap || a != 0.0;
+    }
+    n_ls_capsule += cap ? 1 : 0;
+    const int hn = (d->link_hull && d->hull_vertices) ? d->link_hull[2 * s + 1] : 0;
+    if (hn < 0 || (hn > 0 && (d->link_hull[2 * s] < 0 || d->link_hull[2 * s] + hn > d->n_hull_vertices)))
+    {
+      err = "link_hull: vertex range outside hull_vertices";
+      return TMX_ERR_INVALID;
+    }
+    if (hn > 0 && cap)
+    {
+      err = "a link primitive is at most one of capsule (link_sphere_axes) and convex hull (link_hull)";
+      return TMX_ERR_INVALID;
+    }
+    L.ls_hull.push_back(hn > 0 ? d->link_hull[2 * s] : 0);
+    L.ls_hull.push_back(hn);
+    n_ls_hull += hn > 0 ? 1 : 0;
+  }
+  P.n_ls_hull = n_ls_hull;
+  if (n_ls_hull > 0)
+    L.hullv.assign(d->hull_vertices, d->hull_vertices + (size_t)3 * d->n_hull_vertices);
+  // Capsule links under a cast evaluator (evaluator_type 3 / 4): the swept volume of a capsule is not a capsule, but a capsule IS the
+  // convex hull of its two cap centres rounded by its radius - such links become two-vertex hulls (every evaluator of the problem
+  // then sees them through GJK / EPA; the oracle applies the same rule, oracle/trajprob.hpp constructProblem)
+  {
+    bool cast_term = false;
+    for (int k = 0; k < d->n_terms; ++k)
+      cast_term = cast_term || ((d->terms[k].kind == TMX_TERM_COLLISION_COST || d->terms[k].kind == TMX_TERM_COLLISION_CNT) && d->terms[k].evaluator_type >= 3);
+    if (cast_term && n_ls_capsule > 0)
+    {
+      for (int sp = 0; sp < d->n_link_spheres; ++sp)
+      {
+        const double* a = &L.ls_axis[3 * (size_t)sp];
+        if (a[0] == 0.0 && a[1] == 0.0 && a[2] == 0.0)
+          continue;
+        L.ls_hull[2 * (size_t)sp] = (int)(L.hullv.size() / 3);
+        L.ls_hull[2 * (size_t)sp + 1] = 2;
+        for (int q = 0; q < 3; ++q)
+          L.hullv.push_back(L.ls_center[3 * (size_t)sp + q]);
+        for (int q = 0; q < 3; ++q)
+          L.hullv.push_back(L.ls_center[3 * (size_t)sp + q] + a[q]);
+        L.ls_axis[3 * (size_t)sp] = L.ls_axis[3 * (size_t)sp + 1] = L.ls_axis[3 * (size_t)sp + 2] = 0.0;
+        ++n_ls_hull;
+        --n_ls_capsule;
+      }
+      P.n_ls_hull = n_ls_hull;
+    }
+  }
+  P.n_ls_capsule = n_ls_capsule;
+  for (int o = 0; o < d->n_obstacles; ++o)
+  {
+    for (int q = 0; q < 3; ++q)
+      L.ob_center.push_back(d->obstacles[o].center[q]);
+    L.ob_radius.push_back(d->obstacles[o].radius);
+    for (int q = 0; q < 3; ++q)
+      L.ob_axis.push_back(d->obstacle_axes ? d->obstacle_axes[3 * o + q] : 0.0);
+    bool box = false;
+    for (int q = 0; q < 12; ++q)
+    {
+      const double v = d->obstacle_boxes ? d->obstacle_boxes[12 * o + q] : 0.0;
+      L.ob_box.push_back(v);
+      box = box || (q < 3 && v > 0.0);
+      if (q < 3 && v < 0.0)
+      {
+        err = "obstacle_boxes: negative half extent";
+        return TMX_ERR_INVALID;
+      }
+    }
+    if (box && d->obstacle_axes && (d->obstacle_axes[3 * o] != 0.0 || d->obstacle_axes[3 * o + 1] != 0.0 || d->obstacle_axes[3 * o + 2] != 0.0))
+    {
+      err = "an obstacle is a capsule (obstacle_axes) or a box (obstacle_boxes), not both";
+      return TMX_ERR_INVALID;
+    }
+    const int nt = (d->obstacle_mesh && d->mesh_triangles) ? d->obstacle_mesh[2 * o + 1] : 0;
+    if (nt < 0 || (nt > 0 && (d->obstacle_mesh[2 * o] < 0 || d->obstacle_mesh[2 * o] + nt > d->n_mesh_triangles)))
+    {
+      err = "obstacle_mesh: triangle range outside mesh_triangles";
+      return TMX_ERR_INVALID;
+    }
+    if (nt > 0)
+    {
+      if (box || (d->obstacle_axes && (d->obstacle_axes[3 * o] != 0.0 || d->obstacle_axes[3 * o + 1] != 0.0 || d->obstacle_axes[3 * o + 2] != 0.0)))
+      {
+        err = "an obstacle is at most one of capsule (obstacle_axes), box (obstacle_boxes) and mesh (obstacle_mesh)";
+        return TMX_ERR_INVALID;
+      }
+      double* rec = L.ob_box.data() + 12 * (size_t)o;
+      rec[0] = -1.0;
+      rec[1] = nt;
+      rec[2] = 9.0 * d->obstacle_mesh[2 * o];
+      box = true;  // (counted with the boxes: the same code path)
+    }
+    n_ob_box += box ? 1 : 0;
+  }
+  P.n_ob_box = n_ob_box;
+  if (d->obstacle_mesh && d->mesh_triangles && d->n_mesh_triangles > 0)
+    L.mesh.assign(d->mesh_triangles, d->mesh_triangles + (size_t)9 * d->n_mesh_triangles);
+  return TMX_OK;
+}
+
+// Stage 2: the QP engine, from what the term loop established.  Pure.
+static EngineChoice choose_engine(const Lowered& L, const DevProblem& P, const UploadHooks& hooks)
+{
+  EngineChoice E;
+  bool qp_dense = L.qp_dense, st_terms = L.st_terms;
+  int band = L.band, R2 = L.R2;
+  std::string tv_why;  // what keeps squared velocity-with-time costs on the dense engine
   // TotalTime terms couple all time variables: one global row (HINGE / EQ / INEQ forms) or a dense objective block 2 c g g' over
   // tau[1 .. T-1] (SQUARED form).  Small problems keep the dense engine, bit for bit as before.  A problem over the dense engine's
   // size limit whose ONLY reason for that engine are these terms runs on the block chain instead: the terms become rank-one
   // corrections of the reduced KKT matrix (QpWs::ttn, tmx_qp.h), at any size.  TMX_TOTAL_TIME_CHAIN: "1" the chain at any size,
   // "0" never (the dense engine and its limit).  Problems that need the dense engine for another reason as well (squared
   // velocity-with-time costs, acceleration / jerk rows), banded objectives, function costs and more than TMX_TT_MAX terms stay there.
-  if (tt_terms)
+  if (L.tt_terms)
   {
-    const char* e = std::getenv("TMX_TOTAL_TIME_CHAIN");
-    const bool able = TMX_LINK_ROWS && !qp_dense && !tv_terms && !stencil_rows && band == 0 && !dyn_p && (int)tt_owner.size() <= TMX_TT_MAX;
-    const bool want = (e && e[0] == '1') || (!(e && e[0] == '0') && P.n_max > dense_qp_max_n());
-    tt_chain = able && want;
-    if (!tt_chain)
+    const bool able = TMX_LINK_ROWS && !qp_dense && !L.tv_terms && !L.stencil_rows && band == 0 && !L.dyn_p && (int)L.tt_owner.size() <= TMX_TT_MAX;
+    const bool want = hooks.total_time_chain == '1' || (hooks.total_time_chain != '0' && P.n_max > hooks.dense_qp_max_n);
+    E.tt_chain = able && want;
+    if (!E.tt_chain)
       qp_dense = true;
   }
   // Squared JointVel-with-time costs (exprSquare of a x[t][j] + b x[t+1][j] + c tau[t+1] + k) put entries that change with the iterate
@@ -1351,23 +1426,22 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
   // LVS / cast collision rows) and next to any other row term (QpWs::tvo, tmx_qp.h).  TMX_VEL_TIME_CHAIN: "1" the chain at any size,
   // "0" never (the dense engine and its limit).  Next to TotalTime terms, acceleration / jerk costs or rows, or function costs
   // (their D x D objective blocks live in the per-problem scratch, QpWs::pb, and take another ADMM loop) the dense engine stays.
-  if (tv_terms)
+  if (L.tv_terms)
   {
-    const char* e = std::getenv("TMX_VEL_TIME_CHAIN");
-    const bool able = TMX_LINK_ROWS && !qp_dense && !tt_terms && !stencil_rows && band == 0 && !dyn_p;
-    const bool want = (e && e[0] == '1') || (!(e && e[0] == '0') && P.n_max > dense_qp_max_n());
-    tv_chain = able && want;
-    if (tt_terms)
+    const bool able = TMX_LINK_ROWS && !qp_dense && !L.tt_terms && !L.stencil_rows && band == 0 && !L.dyn_p;
+    const bool want = hooks.vel_time_chain == '1' || (hooks.vel_time_chain != '0' && P.n_max > hooks.dense_qp_max_n);
+    E.tv_chain = able && want;
+    if (L.tt_terms)
       tv_why = " next to TotalTime terms";
-    else if (band != 0 || stencil_rows)
+    else if (band != 0 || L.stencil_rows)
       tv_why = " next to acceleration / jerk costs or rows";
-    else if (dyn_p)
+    else if (L.dyn_p)
       tv_why = " next to function costs";
     else if (qp_dense || !TMX_LINK_ROWS)
       tv_why = " in a build without rows on two waypoints";
     else
       tv_why = " with TMX_VEL_TIME_CHAIN=0";
-    if (!tv_chain)
+    if (!E.tv_chain)
       qp_dense = true;
     else
     {
@@ -1380,209 +1454,197 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
   // LVS / cast collision rows, no CartVel rows) all the blocks they add to the reduced KKT matrix are diagonal, and the problem runs
   // on the banded structured path at any size (band = max of the orders of costs and rows; DevProblem::band_rows).  Next to general
   // pair rows (dense coupling blocks) or to function costs (dynamic P) they keep the dense engine.
-  bool band_rows = false;
-  if (stencil_rows)
+  if (L.stencil_rows)
   {
     int other_pairs = 0;
-    for (int r = 0; r < R; ++r)
-      if (c2[r] >= 0 && !slot_is_diff(kind[r]))
+    for (int r = 0; r < L.R; ++r)
+      if (L.c2[r] >= 0 && !slot_is_diff(L.kind[r]))
         ++other_pairs;
-    if (!qp_dense && other_pairs == 0 && D <= 255)
+    if (!qp_dense && other_pairs == 0 && P.D <= 255)
     {
-      band_rows = true;
+      E.band_rows = true;
       st_terms = true;  // the term code of these rows is instantiated in the piecewise kernels (template flag ST)
-      band = std::max(band, max_row_order);
+      band = std::max(band, L.max_row_order);
     }
     else
       qp_dense = true;
   }
   // squared acceleration / jerk costs alone keep the structured solver (banded block factorisation of the generic path); together
   // with general pair rows (the dense-coupling chain has no banded variant) or function costs: dense engine
-  if (band && !band_rows && (qp_dense || R2 > 0))
+  if (band && !E.band_rows && (qp_dense || R2 > 0))
   {
     qp_dense = true;
     band = 0;
   }
-  P.band = band;
-  P.band_rows = band_rows ? 1 : 0;
-  P.n_stencil = n_stencil;
-  P.qp_dense = qp_dense ? 1 : 0;
-  P.st = (qp_dense || st_terms) ? 1 : 0;
-  P.tt_chain = tt_chain ? (int)tt_owner.size() : 0;
-  P.tt_place = 0;
-  P.tv_chain = tv_chain ? 1 : 0;
-  // convex-hull links: their contact code (GJK / EPA) is instantiated in the piecewise kernels only (template flag HULL)
+  E.qp_dense = qp_dense;
+  E.band = band;
+  E.R2 = R2;
+  // convex-hull links (and capsule links under a cast evaluator, which become hulls): their contact code (GJK / EPA) is instantiated
+  // in the piecewise kernels only (template flag HULL)
+  E.st = qp_dense || st_terms || P.n_ls_hull > 0;
+  if (qp_dense)
   {
-    int n_hull = 0;
-    if (d->link_hull && d->hull_vertices)
-      for (int sp = 0; sp < d->n_link_spheres; ++sp)
-        n_hull += d->link_hull[2 * sp + 1] > 0 ? 1 : 0;
-    if (n_hull > 0)
-      P.st = 1;
+    // what put the problem on the dense engine (TotalTime terms alone do not above its size limit: they run on the block chain unless
+    // one of the reasons below keeps them off it)
+    std::string& why = E.dense_reasons;
+    auto reason = [&why](const std::string& r) { why += (why.empty() ? "" : ", ") + r; };
+    if (!L.tv_owner.empty())
+      reason("squared joint-velocity costs with time" + tv_why);
+    if (L.stencil_rows)
+      reason("acceleration / jerk rows next to collision / CartVel rows on two waypoints or to time-parameterised terms");
+    if (L.tt_terms && (int)L.tt_owner.size() > TMX_TT_MAX)
+      reason("more than " + std::to_string(TMX_TT_MAX) + " TotalTime terms");
+    else if (L.tt_terms && (band != 0 || L.dyn_p))
+      reason("TotalTime terms next to acceleration / jerk costs or function costs");
+    else if (L.tt_terms && L.tv_owner.empty() && !L.stencil_rows)
+      reason("TotalTime terms with TMX_TOTAL_TIME_CHAIN=0 (or a build without rows on two waypoints)");
+    if (why.empty())
+      reason("acceleration / jerk costs next to rows on two waypoints or function costs");
   }
-  P.n_fx = (int)fx_t.size();
-  P.n_fx_cost = n_fx_cost;
-  // slots grouped by waypoint, ascending slot id inside a waypoint
-  std::vector<int> wp_start(T + 1, 0), wp_list(R, 0);
-  for (int r = 0; r < R; ++r)
-    wp_start[st[r] + 1]++;
-  for (int t = 0; t < T; ++t)
-    wp_start[t + 1] += wp_start[t];
+  return E;
+}
+
+// the term / structure kernels' dynamic LDS (bytes)
+static size_t small_smem_bytes(const Lowered& L, const DevProblem& P)
+{
+  const size_t small_ints = 2 * (size_t)(P.n_max + 1) + 4 * (size_t)L.R + 2 + 16 + 16 + 512;  // qp_structure: tables, hash accumulators, chunk totals
+  const size_t small = std::max<size_t>((tmx_eval_scratch_doubles(L.R, P.D * P.T, (int)L.vel_first.size(), L.n_costs, L.n_cnts) + L.n_costs + L.n_cnts + 8) * sizeof(double),
+                                        small_ints * sizeof(int) + 64);
+  return std::max<size_t>(small, tmx_cvx_scratch_doubles(P.n_cp, P.D) * sizeof(double));
+}
+
+// Stage 3: where the QP workspace lives, which thread carries which row, the LDS budgets.  Pure; reads the engine fields of P.
+static Placement place_workspace(const Lowered& L, const EngineChoice& E, const DevProblem& P, const UploadHooks& hooks)
+{
+  Placement pl;
+  const int D = P.D, T = P.T, R = L.R, NA = L.NA, R2 = E.R2;
+  // workspace placement: everything in LDS if it fits; else everything but the row coefficient arrays (they move to the HBM
+  // scratch: config 4, 177 -> 125 KB); else the HBM-workspace kernels
+  // TMX_FORCE_COEF_FAR - test hook: exercise the placement on small problems / the host build
+  if (hooks.force_coef_far == '1' || (qp_smem_bytes(D, T, R, NA, R2, 0) > 160 * 1024 && qp_smem_bytes(D, T, R, NA, R2, 1) <= 160 * 1024))
+    pl.coef_far = 1;
+  // (round 4 also moved the rows of odd block sizes above 8 there, on the hypothesis that 16-byte flat accesses at 8-byte aligned LDS
+  //  addresses fault; the hardware accepts them - tools/ubench/align_probe.hip, profiles/r05/r05a_align_probe.log - and the placement is gone)
   {
-    std::vector<int> next(wp_start.begin(), wp_start.end() - 1);
+    // compact row lists (bit 1 of the flag word): problems whose row slots are mostly collision slots - thousands of slots, a
+    // few hundred contacts at any time (config 3: 15.7 k slots, ~370 active rows).  Such problems never take the dense fast
+    // path (R <= 512), which rebuilds its workspace descriptor without the lists.
+    int n_coll = 0;
+    for (int k : L.kind)
+      n_coll += (k == SLOT_COLLISION || k == SLOT_COLLISION_LVS) ? 1 : 0;
+    // TMX_FORCE_COMPACT - test hook: "1" on (any size > 512 is not required on the host build), "0" off
+    // (pair-row problems never take the dense fast path, so the lists pay at any size: config 4 - 478 slots, ~195 active rows - 17 %)
+    if (hooks.force_compact == '1' || (hooks.force_compact != '0' && (R >= 1024 || R2 > 0) && 2 * n_coll > R))
+      pl.coef_far |= 2;
+  }
+  if (L.dyn_p && !E.qp_dense)
+    pl.coef_far |= 4;  // dynamic objective blocks behind the far region of the per-problem scratch (qp_dynp_offset)
+  // row -> thread assignment of the register-resident bursts (tmx_row_perm.h); TMX_ROW_PERM=0 keeps the slot order
+  if (hooks.row_perm != '0' && R <= 2 * TMX_QP_NT && TMX_QP_NT == 256)
+    pl.row_perm = build_row_perm(R, L.naux, TMX_QP_NT);
+  {
+    // constants of the QP setup (DevProblem::wp_pst / row_epos): the grouped e exchange of the register-resident burst keeps the rows of
+    // waypoint t in wp_list order from the even offset wp_pst[t] on
+    pl.pst.assign(T + 1, 0);
+    pl.epos.assign(R, 0);
+    int acc = 0, rows_max = 0, naux_max = 0;
+    for (int t = 0; t <= T; ++t)
+    {
+      pl.pst[t] = acc;
+      if (t == T)
+        break;
+      const int c = L.wp_start[t + 1] - L.wp_start[t];
+      for (int u = L.wp_start[t]; u < L.wp_start[t + 1]; ++u)
+        pl.epos[L.wp_list[u]] = acc + (u - L.wp_start[t]);
+      acc += c + (c & 1);
+      rows_max = std::max(rows_max, c);
+    }
     for (int r = 0; r < R; ++r)
-      wp_list[next[st[r]]++] = r;
+      naux_max = std::max(naux_max, L.naux[r]);
+    pl.setup_fast = (rows_max <= TMX_SETUP_COL && naux_max <= 2 && R <= 2 * TMX_QP_NT) ? 1 : 0;
   }
-  std::vector<int> ls_link;
-  std::vector<double> ls_center, ls_radius, ob_center, ob_radius, ob_axis, ls_axis, ob_box, hullv;
-  std::vector<int> ls_hull;
-  int n_ls_hull = 0;
-  int n_ls_capsule = 0, n_ob_box = 0;
-  for (int s = 0; s < d->n_link_spheres; ++s)
+  pl.smem_small = small_smem_bytes(L, P);
+#if TMX_IS_DEVICE
   {
-    if (d->link_spheres[s].link < 0 || d->link_spheres[s].link >= D)
+    // a wave pair per problem (tmx_wave.h): block-tridiagonal QPs with diagonal couplings whose row-slot template fits the lane plan.
+    // OPT-IN (TMX_WAVE=1): measured on MI355X (round 6, profiles/r06/) the wave-pair solver runs BASELINE config 1 at 101 k SQP it/s
+    // against the 118 k of k_sqp_pool - its ADMM iteration costs 4.6 k cycles per problem per CU where the stated bar was < 3 k - so
+    // the one-workgroup-per-CU kernels stay the default; DESIGN.md section 5
+    std::vector<int> plan(TMX_WV_NT * TMX_WV_REC, 0);
+    int gmax = 4, aux2 = 0, n3 = 0;
+    if (hooks.wave == '1' && P.flavor == 0 && R2 == 0 && pl.coef_far == 0 && !E.qp_dense && !P.st && !P.band && !P.use_time && P.n_fx == 0 &&
+        wave_plan_build(D, T, R, L.st.data(), L.naux.data(), plan.data(), &gmax, &aux2, &n3))
     {
-      ctx->err = "link sphere attached to an invalid link";
-      return TMX_ERR_INVALID;
-    }
-    ls_link.push_back(d->link_spheres[s].link);
-    for (int q = 0; q < 3; ++q)
-      ls_center.push_back(d->link_spheres[s].center[q]);
-    ls_radius.push_back(d->link_spheres[s].radius);
-    bool cap = false;
-    for (int q = 0; q < 3; ++q)
-    {
-      const double a = d->link_sphere_axes ? d->link_sphere_axes[3 * s + q] : 0.0;
-      ls_axis.push_back(a);
-      cap = cap || a != 0.0;
-    }
-    n_ls_capsule += cap ? 1 : 0;
-    const int hn = (d->link_hull && d->hull_vertices) ? d->link_hull[2 * s + 1] : 0;
-    if (hn < 0 || (hn > 0 && (d->link_hull[2 * s] < 0 || d->link_hull[2 * s] + hn > d->n_hull_vertices)))
-    {
-      ctx->err = "link_hull: vertex range outside hull_vertices";
-      return TMX_ERR_INVALID;
-    }
-    if (hn > 0 && cap)
-    {
-      ctx->err = "a link primitive is at most one of capsule (link_sphere_axes) and convex hull (link_hull)";
-      return TMX_ERR_INVALID;
-    }
-    ls_hull.push_back(hn > 0 ? d->link_hull[2 * s] : 0);
-    ls_hull.push_back(hn);
-    n_ls_hull += hn > 0 ? 1 : 0;
-  }
-  P.n_ls_hull = n_ls_hull;
-  if (n_ls_hull > 0)
-    hullv.assign(d->hull_vertices, d->hull_vertices + (size_t)3 * d->n_hull_vertices);
-  // Capsule links under a cast evaluator (evaluator_type 3 / 4): the swept volume of a capsule is not a capsule, but a capsule IS the
-  // convex hull of its two cap centres rounded by its radius - such links become two-vertex hulls (every evaluator of the problem
-  // then sees them through GJK / EPA; the oracle applies the same rule, oracle/trajprob.hpp constructProblem)
-  {
-    bool cast_term = false;
-    for (int k = 0; k < d->n_terms; ++k)
-      cast_term = cast_term || ((d->terms[k].kind == TMX_TERM_COLLISION_COST || d->terms[k].kind == TMX_TERM_COLLISION_CNT) && d->terms[k].evaluator_type >= 3);
-    if (cast_term && n_ls_capsule > 0)
-    {
-      for (int sp = 0; sp < d->n_link_spheres; ++sp)
+      const size_t lds = std::max(pl.smem_small, wave_lds_doubles(D, T, R) * sizeof(double));
+      if (lds <= 40 * 1024)  // four problems per CU
       {
-        const double* a = &ls_axis[3 * (size_t)sp];
-        if (a[0] == 0.0 && a[1] == 0.0 && a[2] == 0.0)
-          continue;
-        ls_hull[2 * (size_t)sp] = (int)(hullv.size() / 3);
-        ls_hull[2 * (size_t)sp + 1] = 2;
-        for (int q = 0; q < 3; ++q)
-          hullv.push_back(ls_center[3 * (size_t)sp + q]);
-        for (int q = 0; q < 3; ++q)
-          hullv.push_back(ls_center[3 * (size_t)sp + q] + a[q]);
-        ls_axis[3 * (size_t)sp] = ls_axis[3 * (size_t)sp + 1] = ls_axis[3 * (size_t)sp + 2] = 0.0;
-        ++n_ls_hull;
-        --n_ls_capsule;
-      }
-      P.n_ls_hull = n_ls_hull;
-      P.st = 1;
-    }
-  }
-  P.n_ls_capsule = n_ls_capsule;
-  for (int o = 0; o < d->n_obstacles; ++o)
-  {
-    for (int q = 0; q < 3; ++q)
-      ob_center.push_back(d->obstacles[o].center[q]);
-    ob_radius.push_back(d->obstacles[o].radius);
-    for (int q = 0; q < 3; ++q)
-      ob_axis.push_back(d->obstacle_axes ? d->obstacle_axes[3 * o + q] : 0.0);
-    bool box = false;
-    for (int q = 0; q < 12; ++q)
-    {
-      const double v = d->obstacle_boxes ? d->obstacle_boxes[12 * o + q] : 0.0;
-      ob_box.push_back(v);
-      box = box || (q < 3 && v > 0.0);
-      if (q < 3 && v < 0.0)
-      {
-        ctx->err = "obstacle_boxes: negative half extent";
-        return TMX_ERR_INVALID;
+        pl.plan.swap(plan);
+        pl.wave_ok = 1;
+        pl.wv_gmax = gmax;
+        pl.wv_aux2 = aux2;
+        pl.smem_wave = lds;
       }
     }
-    if (box && d->obstacle_axes && (d->obstacle_axes[3 * o] != 0.0 || d->obstacle_axes[3 * o + 1] != 0.0 || d->obstacle_axes[3 * o + 2] != 0.0))
-    {
-      ctx->err = "an obstacle is a capsule (obstacle_axes) or a box (obstacle_boxes), not both";
-      return TMX_ERR_INVALID;
-    }
-    const int nt = (d->obstacle_mesh && d->mesh_triangles) ? d->obstacle_mesh[2 * o + 1] : 0;
-    if (nt < 0 || (nt > 0 && (d->obstacle_mesh[2 * o] < 0 || d->obstacle_mesh[2 * o] + nt > d->n_mesh_triangles)))
-    {
-      ctx->err = "obstacle_mesh: triangle range outside mesh_triangles";
-      return TMX_ERR_INVALID;
-    }
-    if (nt > 0)
-    {
-      if (box || (d->obstacle_axes && (d->obstacle_axes[3 * o] != 0.0 || d->obstacle_axes[3 * o + 1] != 0.0 || d->obstacle_axes[3 * o + 2] != 0.0)))
-      {
-        ctx->err = "an obstacle is at most one of capsule (obstacle_axes), box (obstacle_boxes) and mesh (obstacle_mesh)";
-        return TMX_ERR_INVALID;
-      }
-      double* rec = ob_box.data() + 12 * (size_t)o;
-      rec[0] = -1.0;
-      rec[1] = nt;
-      rec[2] = 9.0 * d->obstacle_mesh[2 * o];
-      box = true;  // (counted with the boxes: the same code path)
-    }
-    n_ob_box += box ? 1 : 0;
   }
-  P.n_ob_box = n_ob_box;
-  std::vector<double> mesh;
-  if (d->obstacle_mesh && d->mesh_triangles && d->n_mesh_triangles > 0)
-    mesh.assign(d->mesh_triangles, d->mesh_triangles + (size_t)9 * d->n_mesh_triangles);
+#endif
+  // LDS budgets
+  pl.smem_qp = qp_smem_bytes(D, T, R, NA, R2, pl.coef_far);
+  if (P.tt_chain > 0 || P.tv_chain)
+  {
+    // per-problem data of the rank-one terms (g, Z = K_chain^-1 g: read by every ADMM iteration) or the joint - time entries of
+    // squared JointVel-with-time costs (read by every factorisation and every product with P): behind the QP workspace when it
+    // stays in LDS with them, or lives in HBM anyway (long horizons); in the per-problem scratch when they alone would push an
+    // LDS-resident workspace out
+    const size_t tt_bytes = ((P.tv_chain ? qp_tv_doubles(D, T) : qp_tt_doubles(D, T, P.tt_chain)) + 2) * sizeof(double);
+    // TMX_TT_PLACE - test hook: "2" = in the per-problem scratch whatever the sizes
+    if (TMX_QP_COLD_IN_LDS && hooks.tt_place != '2' && (pl.smem_qp > 160 * 1024 || pl.smem_qp + tt_bytes <= 160 * 1024))
+    {
+      pl.tt_place = 1;
+      pl.smem_qp += tt_bytes;
+    }
+    else
+    {
+      pl.tt_place = 2;
+      pl.tt_scratch = tt_bytes / sizeof(double);
+    }
+  }
+  return pl;
+}
+
+// Stage 4: every table to the device, in a fixed allocation order (tmx_ctx::prob_allocs), then DevProblem itself.
+static tmx_status upload_tables(tmx_ctx* ctx, const Lowered& L, const Placement& pl, DevProblem& P)
+{
   auto& pool = ctx->prob_allocs;
   tmx_status rc;
 #define UP(field, vec)                                                                                                \
   if ((rc = upload(ctx, pool, &P.field, vec)) != TMX_OK)                                                              \
   return rc
-  UP(slot_kind, kind);
-  UP(slot_t, st);
-  UP(slot_sub, sub);
-  UP(slot_sub2, sub2);
-  UP(slot_owner, owner);
-  UP(slot_naux, naux);
-  UP(slot_aoff, aoff);
-  UP(slot_iscnt, iscnt);
-  UP(slot_eq, iseq);
-  UP(slot_objc, objc);
-  UP(slot_scale, scale);
-  UP(slot_aux1, aux1);
-  UP(slot_aux2, aux2);
-  UP(slot_c2, c2);
-  UP(slot_sub3, sub3);
-  UP(slot_aux3, aux3);
+  UP(slot_kind, L.kind);
+  UP(slot_t, L.st);
+  UP(slot_sub, L.sub);
+  UP(slot_sub2, L.sub2);
+  UP(slot_owner, L.owner);
+  UP(slot_naux, L.naux);
+  UP(slot_aoff, L.aoff);
+  UP(slot_iscnt, L.iscnt);
+  UP(slot_eq, L.iseq);
+  UP(slot_objc, L.objc);
+  UP(slot_scale, L.scale);
+  UP(slot_aux1, L.aux1);
+  UP(slot_aux2, L.aux2);
+  UP(slot_c2, L.c2);
+  UP(slot_sub3, L.sub3);
+  UP(slot_aux3, L.aux3);
   {
     // slot range of every cost / constraint (key = cost index, or n_costs + constraint index)
+    const int n_costs = L.n_costs, n_cnts = L.n_cnts;
     std::vector<int> lo((size_t)(n_costs + n_cnts), 1), hi((size_t)(n_costs + n_cnts), 0);
     std::vector<char> seen((size_t)(n_costs + n_cnts), 0);
-    for (int r = 0; r < static_cast<int>(kind.size()); ++r)
+    for (int r = 0; r < L.R; ++r)
     {
-      if (kind[(size_t)r] == SLOT_FIXED)
+      if (L.kind[(size_t)r] == SLOT_FIXED)
         continue;
-      const int k = iscnt[(size_t)r] ? n_costs + owner[(size_t)r] : owner[(size_t)r];
+      const int k = L.iscnt[(size_t)r] ? n_costs + L.owner[(size_t)r] : L.owner[(size_t)r];
       if (k < 0 || k >= n_costs + n_cnts)
         continue;
       if (!seen[(size_t)k])
@@ -1595,223 +1657,77 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
     UP(own_lo, lo);
     UP(own_hi, hi);
   }
-  P.n_link = R2;
-  P.lvs_kmax = lvs_kmax;
-  UP(wp_start, wp_start);
-  UP(wp_list, wp_list);
-  UP(pd, pd);
-  UP(po, po);
-  UP(pq, pq);
-  UP(ls_axis, ls_axis);
-  UP(ls_hull, ls_hull);
-  UP(hull, hullv);
-  UP(ob_box, ob_box);
-  UP(mesh, mesh);
-  UP(po2, po2);
-  UP(po3, po3);
-  UP(fx_t, fx_t);
-  UP(fx_kind, fx_kind);
-  UP(fx_owner, fx_owner);
-  UP(fx_op0, fx_op0);
-  UP(fx_nops, fx_nops);
-  UP(fx_c0, fx_c0);
-  UP(fx_nout, fx_nout);
-  UP(fx_slot0, fx_slot0);
-  UP(fx_ci, fx_ci);
-  UP(fx_ops, fx_ops);
-  UP(fx_consts, fx_consts);
-  UP(p_colptr, p_colptr);
-  UP(vel_first, vel_first);
-  UP(vel_last, vel_last);
-  UP(vel_cost, vel_cost);
-  UP(vel_kind, vel_kind);
-  UP(vel_coeffs, vel_coeffs);
-  UP(vel_targets, vel_targets);
-  UP(cp_t, cp_t);
-  UP(cp_owner, cp_owner);
-  UP(cp_iscnt, cp_iscnt);
-  UP(cp_nrows, cp_nrows);
-  UP(cp_idx, cp_idx);
-  UP(cp_slot0, cp_slot0);
-  UP(cp_coeff, cp_coeff);
-  UP(cp_target, cp_target);
-  UP(ls_link, ls_link);
-  UP(ls_center, ls_center);
-  UP(ls_radius, ls_radius);
-  UP(ob_center, ob_center);
-  UP(ob_radius, ob_radius);
-  UP(ob_axis, ob_axis);
-  P.n_tv = (int)tv_owner.size();
-  P.n_tt = (int)tt_owner.size();
-  UP(tv_owner, tv_owner);
-  UP(tv_joint, tv_joint);
-  UP(tv_first, tv_first);
-  UP(tv_last, tv_last);
-  UP(tv_coeff, tv_coeff);
-  UP(tv_target, tv_target);
-  UP(tv_up, tv_up);
-  UP(tv_lo, tv_lo);
-  UP(tt_owner, tt_owner);
-  UP(tt_form, tt_form);
-  UP(tt_slot, tt_slot);
-  UP(tt_coeff, tt_coeff);
-  UP(tt_limit, tt_limit);
+  UP(wp_start, L.wp_start);
+  UP(wp_list, L.wp_list);
+  UP(pd, L.pd);
+  UP(po, L.po);
+  UP(pq, L.pq);
+  UP(ls_axis, L.ls_axis);
+  UP(ls_hull, L.ls_hull);
+  UP(hull, L.hullv);
+  UP(ob_box, L.ob_box);
+  UP(mesh, L.mesh);
+  UP(po2, L.po2);
+  UP(po3, L.po3);
+  UP(fx_t, L.fx_t);
+  UP(fx_kind, L.fx_kind);
+  UP(fx_owner, L.fx_owner);
+  UP(fx_op0, L.fx_op0);
+  UP(fx_nops, L.fx_nops);
+  UP(fx_c0, L.fx_c0);
+  UP(fx_nout, L.fx_nout);
+  UP(fx_slot0, L.fx_slot0);
+  UP(fx_ci, L.fx_ci);
+  UP(fx_ops, L.fx_ops);
+  UP(fx_consts, L.fx_consts);
+  UP(p_colptr, L.p_colptr);
+  UP(vel_first, L.vel_first);
+  UP(vel_last, L.vel_last);
+  UP(vel_cost, L.vel_cost);
+  UP(vel_kind, L.vel_kind);
+  UP(vel_coeffs, L.vel_coeffs);
+  UP(vel_targets, L.vel_targets);
+  UP(cp_t, L.cp_t);
+  UP(cp_owner, L.cp_owner);
+  UP(cp_iscnt, L.cp_iscnt);
+  UP(cp_nrows, L.cp_nrows);
+  UP(cp_idx, L.cp_idx);
+  UP(cp_slot0, L.cp_slot0);
+  UP(cp_coeff, L.cp_coeff);
+  UP(cp_target, L.cp_target);
+  UP(ls_link, L.ls_link);
+  UP(ls_center, L.ls_center);
+  UP(ls_radius, L.ls_radius);
+  UP(ob_center, L.ob_center);
+  UP(ob_radius, L.ob_radius);
+  UP(ob_axis, L.ob_axis);
+  UP(tv_owner, L.tv_owner);
+  UP(tv_joint, L.tv_joint);
+  UP(tv_first, L.tv_first);
+  UP(tv_last, L.tv_last);
+  UP(tv_coeff, L.tv_coeff);
+  UP(tv_target, L.tv_target);
+  UP(tv_up, L.tv_up);
+  UP(tv_lo, L.tv_lo);
+  UP(tt_owner, L.tt_owner);
+  UP(tt_form, L.tt_form);
+  UP(tt_slot, L.tt_slot);
+  UP(tt_coeff, L.tt_coeff);
+  UP(tt_limit, L.tt_limit);
+  // the placement: DevProblem::row_perm / wv_plan stay null without a permutation / a lane plan
+  P.coef_far = pl.coef_far;
+  P.setup_fast = pl.setup_fast;
+  P.tt_place = pl.tt_place;
+  P.wave_ok = pl.wave_ok;
+  P.wv_gmax = pl.wv_gmax;
+  P.wv_aux2 = pl.wv_aux2;
+  if (!pl.row_perm.empty())
+    UP(row_perm, pl.row_perm);
+  UP(wp_pst, pl.pst);
+  UP(row_epos, pl.epos);
+  if (pl.wave_ok)
+    UP(wv_plan, pl.plan);
 #undef UP
-  // workspace placement: everything in LDS if it fits; else everything but the row coefficient arrays (they move to the HBM
-  // scratch: config 4, 177 -> 125 KB); else the HBM-workspace kernels
-  P.coef_far = 0;
-  {
-    const char* force = std::getenv("TMX_FORCE_COEF_FAR");  // test hook: exercise the placement on small problems / the host build
-    if ((force && force[0] == '1') ||
-        (qp_smem_bytes(D, T, R, NA, R2, 0) > 160 * 1024 && qp_smem_bytes(D, T, R, NA, R2, 1) <= 160 * 1024))
-      P.coef_far = 1;
-    // (round 4 also moved the rows of odd block sizes above 8 there, on the hypothesis that 16-byte flat accesses at 8-byte aligned LDS
-    //  addresses fault; the hardware accepts them - tools/ubench/align_probe.hip, profiles/r05/r05a_align_probe.log - and the placement is gone)
-  }
-  {
-    // compact row lists (bit 1 of the flag word): problems whose row slots are mostly collision slots - thousands of slots, a
-    // few hundred contacts at any time (config 3: 15.7 k slots, ~370 active rows).  Such problems never take the dense fast
-    // path (R <= 512), which rebuilds its workspace descriptor without the lists.
-    int n_coll = 0;
-    for (int k : kind)
-      n_coll += (k == SLOT_COLLISION || k == SLOT_COLLISION_LVS) ? 1 : 0;
-    const char* force = std::getenv("TMX_FORCE_COMPACT");  // test hook: "1" on (any size > 512 is not required on the host build), "0" off
-    // (pair-row problems never take the dense fast path, so the lists pay at any size: config 4 - 478 slots, ~195 active rows - 17 %)
-    const bool on = (force && force[0] == '1') || (!(force && force[0] == '0') && (R >= 1024 || R2 > 0) && 2 * n_coll > R);
-    if (on)
-      P.coef_far |= 2;
-  }
-  if (dyn_p && !qp_dense)
-    P.coef_far |= 4;  // dynamic objective blocks behind the far region of the per-problem scratch (qp_dynp_offset)
-  // a wave pair per problem (tmx_wave.h): block-tridiagonal QPs with diagonal couplings whose row-slot template fits the lane plan
-  P.dbg_flags = 0;
-  P.wave_ok = 0;
-  P.wv_gmax = 2;
-  P.wv_aux2 = 0;
-  P.wv_plan = nullptr;
-  P.row_perm = nullptr;
-  {
-    // ROW -> THREAD assignment of the register-resident bursts (DevProblem::row_perm, tmx_part.h).  With R > 256 row slots the last
-    // R - 256 threads carry two rows.  In slot order those threads got the LAST slots - for config 1 the 65 abs rows (two slack
-    // variables each): one wave ran two rows x (row + two slacks) = six dependent chains per thread in phases A / C of every ADMM
-    // iteration while the other three ran two, and waited (tools/prof_loop.py: 2.0 k of the iteration's 4.7 k cycles).  Here the
-    // two-row threads (and the single-row threads of their waves) take one-slack rows, the two-slack rows go to single-row threads of
-    // the waves below, top down: at most four chains per thread anywhere.  TMX_ROW_PERM=0 keeps the slot order.
-    const char* env = std::getenv("TMX_ROW_PERM");
-    const int NT = TMX_QP_NT;
-    if (!(env && env[0] == '0') && R <= 2 * NT && TMX_QP_NT == 256)
-    {
-      std::vector<int> perm(2 * (size_t)NT, -1), cheap, heavy;
-      for (int r = 0; r < R; ++r)
-        (naux[r] > 1 ? heavy : cheap).push_back(r);
-      const int extra = std::max(0, R - NT), two_first = NT - extra;
-      const int prot_first = extra > 0 ? (two_first / 64) * 64 : NT;  // single-row threads [prot_first, two_first) share a wave with two-row threads
-      std::vector<int> pool(cheap);
-      pool.insert(pool.end(), heavy.begin(), heavy.end());  // (two-slack rows only if the one-slack rows run out)
-      size_t take = 0;
-      for (int q = 0; q < 2; ++q)
-        for (int i = 0; i < extra; ++i)
-          perm[(size_t)q * NT + two_first + i] = pool[take++];
-      for (int tdx = prot_first; tdx < two_first && take < pool.size(); ++tdx)
-        perm[tdx] = pool[take++];
-      // the rest on the threads below: one-slack rows bottom up in slot order, two-slack rows top down (as few waves as possible run the
-      // two-slot instantiation)
-      const int n_free = std::min(prot_first, two_first);
-      const size_t n_cheap_left = take < cheap.size() ? cheap.size() - take : 0, n_left = pool.size() - take, n_heavy_left = n_left - n_cheap_left;
-      if ((int)n_left > n_free)  // (cannot happen: R - 2 extra - (two_first - prot_first) <= prot_first; kept as a guard)
-        perm.clear();
-      else
-      {
-        for (size_t i = 0; i < n_cheap_left; ++i)
-          perm[i] = pool[take + i];
-        for (size_t i = 0; i < n_heavy_left; ++i)
-          perm[(size_t)n_free - n_heavy_left + i] = pool[take + n_cheap_left + i];
-      }
-      if (!perm.empty())
-      {
-        tmx_status rcp;
-        if ((rcp = upload(ctx, ctx->prob_allocs, &P.row_perm, perm)) != TMX_OK)
-          return rcp;
-      }
-    }
-  }
-  P.wp_pst = P.row_epos = nullptr;
-  P.setup_fast = 0;
-  {
-    // constants of the QP setup (DevProblem::wp_pst / row_epos): the grouped e exchange of the register-resident burst keeps the rows of
-    // waypoint t in wp_list order from the even offset wp_pst[t] on
-    std::vector<int> pst(T + 1, 0), epos(R, 0);
-    int acc = 0, rows_max = 0, naux_max = 0;
-    for (int t = 0; t <= T; ++t)
-    {
-      pst[t] = acc;
-      if (t == T)
-        break;
-      const int c = wp_start[t + 1] - wp_start[t];
-      for (int u = wp_start[t]; u < wp_start[t + 1]; ++u)
-        epos[wp_list[u]] = acc + (u - wp_start[t]);
-      acc += c + (c & 1);
-      rows_max = std::max(rows_max, c);
-    }
-    for (int r = 0; r < R; ++r)
-      naux_max = std::max(naux_max, naux[r]);
-    tmx_status rcs;
-    if ((rcs = upload(ctx, ctx->prob_allocs, &P.wp_pst, pst)) != TMX_OK || (rcs = upload(ctx, ctx->prob_allocs, &P.row_epos, epos)) != TMX_OK)
-      return rcs;
-    P.setup_fast = (rows_max <= TMX_SETUP_COL && naux_max <= 2 && R <= 2 * TMX_QP_NT) ? 1 : 0;
-  }
-#if TMX_IS_DEVICE
-  {
-    // OPT-IN (TMX_WAVE=1): measured on MI355X (round 6, profiles/r06/) the wave-pair solver runs BASELINE config 1 at 101 k SQP it/s
-    // against the 118 k of k_sqp_pool - its ADMM iteration costs 4.6 k cycles per problem per CU where the stated bar was < 3 k - so
-    // the one-workgroup-per-CU kernels stay the default; DESIGN.md section 5
-    const char* env = std::getenv("TMX_WAVE");
-    const bool allowed = env && env[0] == '1';
-    std::vector<int> plan(TMX_WV_NT * TMX_WV_REC, 0);
-    int gmax = 4, aux2 = 0, n3 = 0;
-    if (allowed && P.flavor == 0 && R2 == 0 && P.coef_far == 0 && !qp_dense && !P.st && !P.band && !P.use_time && P.n_fx == 0 &&
-        wave_plan_build(D, T, R, st.data(), naux.data(), plan.data(), &gmax, &aux2, &n3))
-    {
-      const size_t small_ints_w = 2 * (size_t)(P.n_max + 1) + 4 * (size_t)R + 2 + 16 + 16 + 512;
-      size_t small = std::max<size_t>((tmx_eval_scratch_doubles(R, D * T, (int)vel_first.size(), n_costs, n_cnts) + n_costs + n_cnts + 8) * sizeof(double),
-                                      small_ints_w * sizeof(int) + 64);
-      small = std::max<size_t>(small, tmx_cvx_scratch_doubles(P.n_cp, D) * sizeof(double));
-      const size_t lds = std::max(small, wave_lds_doubles(D, T, R) * sizeof(double));
-      if (lds <= 40 * 1024)  // four problems per CU
-      {
-        tmx_status rcw;
-        if ((rcw = upload(ctx, ctx->prob_allocs, &P.wv_plan, plan)) != TMX_OK)
-          return rcw;
-        P.wave_ok = 1;
-        P.wv_gmax = gmax;
-        P.wv_aux2 = aux2;
-        ctx->smem_wave = lds;
-      }
-    }
-  }
-#endif
-  // LDS budgets
-  ctx->smem_qp = qp_smem_bytes(D, T, R, NA, R2, P.coef_far);
-  ctx->tt_scratch = 0;
-  if (P.tt_chain > 0 || P.tv_chain)
-  {
-    // per-problem data of the rank-one terms (g, Z = K_chain^-1 g: read by every ADMM iteration) or the joint - time entries of
-    // squared JointVel-with-time costs (read by every factorisation and every product with P): behind the QP workspace when it
-    // stays in LDS with them, or lives in HBM anyway (long horizons); in the per-problem scratch when they alone would push an
-    // LDS-resident workspace out
-    const size_t tt_bytes = ((P.tv_chain ? qp_tv_doubles(D, T) : qp_tt_doubles(D, T, P.tt_chain)) + 2) * sizeof(double);
-    const char* force = std::getenv("TMX_TT_PLACE");  // test hook: "2" = in the per-problem scratch whatever the sizes
-    if (TMX_QP_COLD_IN_LDS && !(force && force[0] == '2') && (ctx->smem_qp > 160 * 1024 || ctx->smem_qp + tt_bytes <= 160 * 1024))
-    {
-      P.tt_place = 1;
-      ctx->smem_qp += tt_bytes;
-    }
-    else
-    {
-      P.tt_place = 2;
-      ctx->tt_scratch = tt_bytes / sizeof(double);
-    }
-  }
   if (!ctx->dp)
   {
     void* p = nullptr;
@@ -1819,56 +1735,45 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
     ctx->dp = static_cast<DevProblem*>(p);
   }
   HIPCHK(hipMemcpy(ctx->dp, &P, sizeof(DevProblem), hipMemcpyHostToDevice));
-  if (std::getenv("TMX_VERBOSE"))
+  return TMX_OK;
+}
+
+// Stage 5: the context's launch configuration - LDS budgets, the dense engine's size limit, kernel attributes, pool size.
+static tmx_status configure_launch(tmx_ctx* ctx, const DevProblem& P, const Lowered& L, const EngineChoice& E, const Placement& pl, const UploadHooks& hooks)
+{
+  const int D = P.D, T = P.T, R = L.R, NA = L.NA, R2 = E.R2;
+  ctx->smem_qp = pl.smem_qp;
+  ctx->tt_scratch = pl.tt_scratch;
+  if (pl.wave_ok)
+    ctx->smem_wave = pl.smem_wave;
+  if (hooks.verbose)
     std::fprintf(stderr, "[tmx] QP engine: %s; TotalTime terms %d, as rank-one terms on the block chain %d; squared velocity-with-time cost instances %d, "
                          "on the dense-coupling block chain %d (data of either %s)\n",
                  P.qp_dense ? "dense" : (P.st ? "structured, piecewise driver" : "structured"), P.n_tt, P.tt_chain, P.n_tv, P.tv_chain,
                  P.tt_place == 1 ? "behind the QP workspace" : (P.tt_place == 2 ? "in the per-problem scratch" : "-"));
-  if (std::getenv("TMX_VERBOSE"))
+  if (hooks.verbose)
     std::fprintf(stderr, "[tmx] problem: D %d (joints %d), T %d, row slots %d, aux %d, pair rows %d, workspace flags %d, band %d, dense %d, QP workspace %zu B, wave-pair solver %d (LDS %zu B, largest lane group %d, second slack in row slots 0x%x)\n", D, P.DK, T, R, NA, R2,
                  P.coef_far, P.band, (int)P.qp_dense, ctx->smem_qp, P.wave_ok, ctx->smem_wave, P.wv_gmax, P.wv_aux2);
-  const size_t small_ints = 2 * (size_t)(P.n_max + 1) + 4 * (size_t)R + 2 + 16 + 16 + 512;  // qp_structure: tables, hash accumulators, chunk totals
-  ctx->smem_small = std::max<size_t>((tmx_eval_scratch_doubles(R, D * T, (int)vel_first.size(), n_costs, n_cnts) + n_costs + n_cnts + 8) * sizeof(double),
-                                     small_ints * sizeof(int) + 64);
-  ctx->smem_small = std::max<size_t>(ctx->smem_small, tmx_cvx_scratch_doubles(P.n_cp, D) * sizeof(double));
+  ctx->smem_small = pl.smem_small;
   ctx->dense = P.qp_dense != 0;
   ctx->piecewise = P.st != 0;
   ctx->band = P.band != 0;
   ctx->hull = P.n_ls_hull > 0;
   ctx->wave = P.wave_ok != 0;
-  ctx->tt_squared = std::find(tt_form.begin(), tt_form.end(), 0) != tt_form.end();
-  if (ctx->dense)
+  ctx->tt_squared = std::find(L.tt_form.begin(), L.tt_form.end(), 0) != L.tt_form.end();
+  // The dense engine inverts n x n (every rho update) and (n + active rows)^2 (polish) matrices by Gauss-Jordan, one workgroup per
+  // problem on an HBM-resident matrix: fine for the few-hundred-variable QPs of the reference's KATs, minutes per batch at the
+  // size of BASELINE config 1 with smoothing costs (n = 572: a 64-seed batch did not finish in 800 s).  Refuse instead of hanging;
+  // TMX_DENSE_QP_MAX_N lifts the limit for callers who accept the time.
+  if (ctx->dense && P.n_max > hooks.dense_qp_max_n)
   {
-    // The dense engine inverts n x n (every rho update) and (n + active rows)^2 (polish) matrices by Gauss-Jordan, one workgroup per
-    // problem on an HBM-resident matrix: fine for the few-hundred-variable QPs of the reference's KATs, minutes per batch at the
-    // size of BASELINE config 1 with smoothing costs (n = 572: a 64-seed batch did not finish in 800 s).  Refuse instead of hanging;
-    // TMX_DENSE_QP_MAX_N lifts the limit for callers who accept the time.
-    if (P.n_max > dense_qp_max_n())
-    {
-      // what put the problem on the dense engine (TotalTime terms alone do not at this size: they run on the block chain unless one
-      // of the reasons below keeps them off it)
-      std::string why;
-      auto reason = [&why](const std::string& r) { why += (why.empty() ? "" : ", ") + r; };
-      if (P.n_tv > 0)
-        reason("squared joint-velocity costs with time" + tv_why);
-      if (stencil_rows)
-        reason("acceleration / jerk rows next to collision / CartVel rows on two waypoints or to time-parameterised terms");
-      if (tt_terms && (int)tt_owner.size() > TMX_TT_MAX)
-        reason("more than " + std::to_string(TMX_TT_MAX) + " TotalTime terms");
-      else if (tt_terms && (band != 0 || dyn_p))
-        reason("TotalTime terms next to acceleration / jerk costs or function costs");
-      else if (tt_terms && P.n_tv == 0 && !stencil_rows)
-        reason("TotalTime terms with TMX_TOTAL_TIME_CHAIN=0 (or a build without rows on two waypoints)");
-      if (why.empty())
-        reason("acceleration / jerk costs next to rows on two waypoints or function costs");
-      ctx->err = why + ": the QP of this problem has too many variables for the dense engine to solve in practical time (limit 448 incl. "
-                 "penalty variables; TMX_DENSE_QP_MAX_N overrides); TotalTime terms alone (up to " + std::to_string(TMX_TT_MAX) + "), squared "
-                 "joint-velocity costs with time (alone, next to rows on two waypoints and to other row terms), function costs, "
-                 "smoothing costs, acceleration / jerk limits and function terms that are rows (constraints, ABS / HINGE costs, AvoidSingularity, "
-                 "DynamicCartPose) have no such limit";
-      ctx->have_problem = false;
-      return TMX_ERR_UNSUPPORTED;
-    }
+    ctx->err = E.dense_reasons + ": the QP of this problem has too many variables for the dense engine to solve in practical time (limit 448 incl. "
+               "penalty variables; TMX_DENSE_QP_MAX_N overrides); TotalTime terms alone (up to " + std::to_string(TMX_TT_MAX) + "), squared "
+               "joint-velocity costs with time (alone, next to rows on two waypoints and to other row terms), function costs, "
+               "smoothing costs, acceleration / jerk limits and function terms that are rows (constraints, ABS / HINGE costs, AvoidSingularity, "
+               "DynamicCartPose) have no such limit";
+    ctx->have_problem = false;
+    return TMX_ERR_UNSUPPORTED;
   }
   if (ctx->dense)
     ctx->smem_small = std::max<size_t>(ctx->smem_small, 320 * sizeof(double));  // reduction scratch of qp_generic_block
@@ -1881,7 +1786,7 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
   // long-horizon problems (config 2: T = 300): neither the QP workspace nor the term scratch fits the 160 KB of LDS;
   // every kernel then carves its scratch from a per-workgroup HBM slice (k_*_hbm for the QP / fused kernels)
   ctx->ws_in_hbm = ctx->smem_qp > 160 * 1024;
-  ctx->ws_bytes = ctx->ws_in_hbm ? std::max({ ctx->smem_qp, ctx->smem_small, (size_t)(n_costs + n_cnts + 8) * sizeof(double) }) : 0;
+  ctx->ws_bytes = ctx->ws_in_hbm ? std::max({ ctx->smem_qp, ctx->smem_small, (size_t)(L.n_costs + L.n_cnts + 8) * sizeof(double) }) : 0;
   if (ctx->ws_in_hbm)
     ctx->smem_small = 64;
   ctx->smem_chain = 0;
@@ -1934,12 +1839,78 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
       ctx->pool_wgs = std::max(1, std::atoi(e));
     if (const char* e = std::getenv("TMX_SQP_MODE"))  // tuning hook: 0 stepwise launches, 1 fused in-order, 2 pool
       ctx->mode = std::max(0, std::min(2, std::atoi(e)));
-    if (std::getenv("TMX_VERBOSE"))
+    if (hooks.verbose)
       std::fprintf(stderr, "[tmx] CUs %d, pool workgroups/CU %d, pool size %d, LDS %zu B\n", cus, per_cu, ctx->pool_wgs, ctx->smem_pool);
   }
 #endif
   ctx->have_problem = true;
   return TMX_OK;
+}
+
+tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx_sqp_params* sqp, const tmx_osqp_settings* osqp)
+{
+  if (!ctx || !d)
+    return TMX_ERR_INVALID;
+  TMX_REFUSE_WHILE_PENDING(ctx);
+  HIPCHK(hipSetDevice(ctx->device));
+  const UploadHooks hooks = UploadHooks::read();
+  // DK joints; D variables per waypoint (time-parameterised problems carry the time variable 1 / dt behind the joints)
+  const int DK = d->n_dof, T = d->n_steps;
+  const int D = DK + (d->use_time ? 1 : 0);
+  if (DK < 1 || D > TMX_MAX_DOF || T < 1)
+  {
+    ctx->err = "n_dof (+ 1 with use_time) must be in [1, TMX_MAX_DOF] and n_steps >= 1";
+    return TMX_ERR_INVALID;
+  }
+  if (d->use_time && (d->dt_lower_lim <= 0 || d->dt_upper_lim < d->dt_lower_lim))
+  {
+    // ProblemConstructionInfo::readBasicInfo  problem_description.cpp:129-133
+    ctx->err = "dt limits (Basic Info) invalid. The lower limit must be positive, and the minimum upper limit is equal to the lower limit.";
+    return TMX_ERR_INVALID;
+  }
+  {
+    // ConstructProblem  problem_description.cpp:415-452: a term that uses time <=> basic_info.use_time
+    bool term_time = false;
+    for (int k = 0; k < d->n_terms && d->terms; ++k)
+      term_time = term_time || d->terms[k].kind == TMX_TERM_JOINT_VEL_TIME || d->terms[k].kind == TMX_TERM_TOTAL_TIME;
+    if (term_time && !d->use_time)
+    {
+      ctx->err = "A term is using time and basic_info is not set correctly. Try basic_info.use_time = true";
+      return TMX_ERR_INVALID;
+    }
+    // (the converse - "No terms use time and basic_info is not set correctly" - is a check on the TermInfo FLAGS in the reference: a
+    //  joint_pos term listed with use_time switches the time column on without ever touching it, problem_description.cpp:1124-1125;
+    //  the front ends make that check, the term table cannot)
+  }
+  if (d->n_fixed_steps < 0 || d->n_fixed_dofs < 0 || d->n_terms < 0 || d->n_link_spheres < 0 || d->n_obstacles < 0 ||
+      (d->n_fixed_steps > 0 && !d->fixed_steps) || (d->n_fixed_dofs > 0 && !d->fixed_dofs) || (d->n_terms > 0 && !d->terms) ||
+      (d->n_link_spheres > 0 && !d->link_spheres) || (d->n_obstacles > 0 && !d->obstacles))
+  {
+    ctx->err = "tmx_problem_desc: negative count or NULL array with a positive count";
+    return TMX_ERR_INVALID;
+  }
+  free_pool(ctx->prob_allocs);
+  free_pool(ctx->batch_allocs);
+  ctx->Bcap = 0;
+  ctx->have_problem = false;
+  DevProblem& P = ctx->hp;
+  fill_basic_info(d, sqp, osqp, P);
+  Lowered L;
+  tmx_status rc;
+  if ((rc = lower_terms(d, P, L, ctx->err)) != TMX_OK)
+    return rc;
+  const EngineChoice E = choose_engine(L, P, hooks);
+  P.band = E.band;
+  P.band_rows = E.band_rows ? 1 : 0;
+  P.qp_dense = E.qp_dense ? 1 : 0;
+  P.st = E.st ? 1 : 0;
+  P.tt_chain = E.tt_chain ? (int)L.tt_owner.size() : 0;
+  P.tv_chain = E.tv_chain ? 1 : 0;
+  P.n_link = E.R2;
+  const Placement pl = place_workspace(L, E, P, hooks);
+  if ((rc = upload_tables(ctx, L, pl, P)) != TMX_OK)
+    return rc;
+  return configure_launch(ctx, P, L, E, pl, hooks);
 }
 
 static tmx_status ensure_batch(tmx_ctx* ctx, int B)

@@ -146,7 +146,7 @@ struct DevProblem
   int wv_aux2;   // bit i: some lane's row slot i holds a row with two slack variables
   int* wv_plan;
   // ROW -> THREAD assignment of the register-resident ADMM bursts (tmx_part.h; round 6): row_perm[q * 256 + tid] = row slot held by thread
-  // tid as its q-th row (-1: none), built at upload from the slack counts of the slots (build_row_perm): the rows beyond 256 pair up
+  // tid as its q-th row (-1: none), built at upload from the slack counts of the slots (build_row_perm, tmx_row_perm.h): the rows beyond 256 pair up
   // ONE-slack rows on the last threads and the two-slack rows sit on single-row threads of other waves, so that no wave runs two rows
   // with two slack variables each per thread.  nullptr: thread tid holds row tid, the rows beyond 256 sit on the last threads
   int* row_perm;

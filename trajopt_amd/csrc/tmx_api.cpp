@@ -1562,6 +1562,15 @@ static Placement place_workspace(const Lowered& L, const EngineChoice& E, const 
     for (int r = 0; r < R; ++r)
       naux_max = std::max(naux_max, L.naux[r]);
     pl.setup_fast = (rows_max <= TMX_SETUP_COL && naux_max <= 2 && R <= 2 * TMX_QP_NT) ? 1 : 0;
+    // the register-resident polish (tmx_polish.h) lays its exchange buffers and flags over the G region of the dense fast path
+    pl.polish_fast = 0;
+    if (pl.setup_fast && dpart_fits(D, T) && R2 == 0)
+    {
+      DPart dp;
+      dpart_make(T, dp);
+      const size_t gn = (size_t)dp.Lmax * D, g_doubles = (size_t)dp.P * gn * dpart_gstride((int)gn);
+      pl.polish_fast = polish_fast_doubles(T, D * T, R, NA, acc + TMX_SETUP_COL) <= g_doubles ? 1 : 0;
+    }
   }
   pl.smem_small = small_smem_bytes(L, P);
 #if TMX_IS_DEVICE
@@ -1717,6 +1726,7 @@ static tmx_status upload_tables(tmx_ctx* ctx, const Lowered& L, const Placement&
   // the placement: DevProblem::row_perm / wv_plan stay null without a permutation / a lane plan
   P.coef_far = pl.coef_far;
   P.setup_fast = pl.setup_fast;
+  P.polish_fast = pl.polish_fast;
   P.tt_place = pl.tt_place;
   P.wave_ok = pl.wave_ok;
   P.wv_gmax = pl.wv_gmax;
@@ -3272,7 +3282,7 @@ __attribute__((visibility("default"))) tmx_status tmx_debug_admm_iters(tmx_ctx* 
 }
 
 // debug hook (not in include/tmx.h): diagnostic switches of the uploaded problem (DevProblem::dbg_flags); bit 0 = scalar assembly of the
-// diagonal KKT blocks instead of the MFMA one
+// diagonal KKT blocks instead of the MFMA one, bit 1 = generic QP setup, bit 2 = generic polish on the dense fast path
 __attribute__((visibility("default"))) tmx_status tmx_debug_set_flags(tmx_ctx* ctx, int flags)
 {
   if (!ctx || !ctx->have_problem || !ctx->dp)
@@ -3291,6 +3301,15 @@ __attribute__((visibility("default"))) int tmx_debug_setup_fast(tmx_ctx* ctx)
   if (!ctx || !ctx->have_problem)
     return -1;
   return ctx->hp.setup_fast;
+}
+
+// debug hook (not in include/tmx.h): 1 when the uploaded problem qualifies for the register-resident polish of the dense fast path
+// (DevProblem::polish_fast; the kernels add their own fast-path predicate), 0 when not, -1 without a problem
+__attribute__((visibility("default"))) int tmx_debug_polish_fast(tmx_ctx* ctx)
+{
+  if (!ctx || !ctx->have_problem)
+    return -1;
+  return ctx->hp.polish_fast;
 }
 
 // debug hook (not in include/tmx.h): 1 = fused persistent optimize() kernel (default), 0 = one launch chain per step

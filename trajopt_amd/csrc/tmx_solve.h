@@ -3,6 +3,7 @@
 #pragma once
 #include "tmx_qp.h"
 #include "tmx_setup.h"
+#include "tmx_polish.h"
 #include "tmx_terms.h"
 
 #if TMX_IS_DEVICE
@@ -1094,6 +1095,32 @@ __device__ __attribute__((noinline)) static double qp_ruiz_fast_nl(const DevProb
   qp_ws_carve(w, smem, scratch + qp_far_doubles(D, T, R, P->NA, P->n_link, P->coef_far), scratch, D, T, R, P->NA, P->n_link, P->coef_far);
 #endif
   return ruiz_fast(w, P, P->osqp.scaling, Bt->dims[4 * b], tid);
+}
+#endif
+// The register-resident polish of the dense fast path (tmx_polish.h) as a function of its own, entered once per QP solve: its row and
+// column registers do not join the allocation of the kernel's cold code; in / out through the LDS record (info).
+// TMX_POLISH_OUTLINED=0 compiles it inline (A/B switch).
+#ifndef TMX_POLISH_OUTLINED
+#define TMX_POLISH_OUTLINED 1
+#endif
+#if TMX_POLISH_OUTLINED
+__device__ __attribute__((noinline)) static void qp_polish_fast_nl(const DevProblem* P_in, const DevBatch* Bt_in, int b_in, unsigned lds_in)
+{
+  const DevProblem* P = tmx_uniform_ptr(P_in);
+  const DevBatch* Bt = tmx_uniform_ptr(Bt_in);
+  const int b = __builtin_amdgcn_readfirstlane(b_in);
+  const int tid = threadIdx.x;
+  double* smem = (double*)(tmx_lds_d*)(size_t)(unsigned)__builtin_amdgcn_readfirstlane((int)lds_in);
+  QpWs w;
+  QpShared* sh = qp_ws_rebuild(w, P, Bt, b, smem);
+  QpInfo info = sh->info;
+  TMX_PROF_ENTER(sh);
+  polish_fast(w, P, P->osqp.delta, P->osqp.polish_refine_iter, info, tid, pc, tlast);
+  TMX_TICK(7);
+  if (tid == 0)
+    sh->info = info;
+  TMX_PROF_LEAVE(sh);
+  TMX_SYNC();
 }
 #endif
 // between two bursts (iteration `iter` just done): returns 1 when the loop ends
@@ -2256,6 +2283,31 @@ TMX_DEVFN void qp_solve_block(const DevProblem* P, const DevBatch* Bt, int b, do
   // ---------------- polish (polish.c) ---------------------------------------------------------------------
   if (TMX_UNI_B(st.polishing && info.status == 1))
   {
+#if TMX_IS_DEVICE
+  // the dense fast path: rows, variables and the polished iterate in registers (tmx_polish.h).  DevProblem::dbg_flags bit 2 keeps the
+  // generic polish below: same bits
+  if (TMX_UNI_B(fast && P->polish_fast != 0 && !(P->dbg_flags & 4) && w.WL == nullptr))
+  {
+#if TMX_ADMM_OUTLINED && TMX_POLISH_OUTLINED
+    QpShared* sh = reinterpret_cast<QpShared*>(w.wself);
+    if (tid == 0)
+      sh->info = info;
+    TMX_SYNC();
+    unsigned lds_off = (unsigned)(size_t)smem;  // (opaque: see the call of qp_admm_fast_nl above)
+    TMX_ASM_OPAQUE_SGPR(lds_off);
+    qp_polish_fast_nl(P, Bt, b, lds_off);
+#ifdef TMX_PROFILE
+    tlast = TMX_CLK();
+#endif
+    info = sh->info;
+    TMX_SYNC();
+#else
+    polish_fast(w, P, st.delta, st.polish_refine_iter, info, tid, pc, tlast);
+#endif
+  }
+  else
+#endif
+  {
     const double delta = st.delta;
     // The polished iterate (dx | dy), the aux right-hand side and the active-set flags normally live in the per-problem
     // HBM scratch; the ADMM factors G / Zs are dead by now, so on the fast path the polish keeps them in that LDS region
@@ -2540,6 +2592,7 @@ TMX_DEVFN void qp_solve_block(const DevProblem* P, const DevBatch* Bt, int b, do
         w.flg_ba[a] = wp.flg_ba[a];
     }
     TMX_SYNC();
+  }
   }
 
   TMX_TICK(7);

@@ -1,10 +1,12 @@
 """Phase profile (needs a -DTMX_PROFILE build: make -C trajopt_amd/csrc EXTRA=-DTMX_PROFILE).
    python tools/prof_phases.py [B] [full|first] [lib.so] [config[s]]   - first QP solve only (default) or the whole optimize() run
-   ("full"); config 1 (default), 2, 3 or 4"""
+   ("full"); config 1 (default), 2, 3 or 4; the word "fine5" anywhere among the arguments names the slots of a -DTMX_PROFILE -DTMX_FINE=5 build"""
 import sys, os, ctypes as C, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from trajopt_amd import configs, abi, runtime
+fine5 = "fine5" in sys.argv[1:]  # (a word, not a position: taken out before the positional arguments are read)
+sys.argv = [a for a in sys.argv if a != "fine5"]
 smooth = len(sys.argv) > 4 and sys.argv[4].endswith("s")  # "1s": config 1 + acceleration and jerk smoothing costs (banded path)
 cid = int(sys.argv[4].rstrip("s")) if len(sys.argv) > 4 else 1
 pci, s, g = {1: configs.config1, 2: configs.config2, 3: configs.config3, 4: configs.config4}[cid]()
@@ -36,6 +38,12 @@ ctx.lib.tmx_debug_phase_cycles.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)]
 ctx.lib.tmx_debug_phase_cycles(ctx.h, out)
 names = ["setup", "WALL(10ns)", "ADMM loop | generic: phase A", "check_term | generic: phase B", "convexify_terms | generic: chain", "generic: phase C", "residuals+rho", "polish", "burst entry", "burst exit",
          "store", "qp_structure", "eval+update", "f:assemble", "f:G inverses", "f:Schur+Zs"]
+# -DTMX_PROFILE -DTMX_FINE=5 builds (pass "fine5" as the last argument): the SQP shell around the QP solve split over the reused slots.
+# As with TMX_FINE=1, the reused slots keep their own phases: subtract the rows of a plain -DTMX_PROFILE run of the same commit.
+if fine5:
+    names[11], names[12] = "qp_structure: P hashes + reduction", "eval+update: decision + log + accept copy"
+    names[13], names[14] = "f:assemble + eval+update: exact evaluation", "f:G inverses + eval+update: model values"
+    names[15], names[6] = "f:Schur+Zs + qp_structure: prefix counts + column pointers", "residuals+rho + qp_structure: hashing walks of A"
 out = list(out)
 # Slot 5 is a phase TIME only on the generic path ("phase C").  On the dense fast path (config 1 without smoothing costs) the
 # epoch-resident burst uses it as a COUNTER (tmx_part.h: pc[5] += 1 + (go_on << 20) per in-register check): decode it and keep it

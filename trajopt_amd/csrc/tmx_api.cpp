@@ -1571,6 +1571,15 @@ static Placement place_workspace(const Lowered& L, const EngineChoice& E, const 
       const size_t gn = (size_t)dp.Lmax * D, g_doubles = (size_t)dp.P * gn * dpart_gstride((int)gn);
       pl.polish_fast = polish_fast_doubles(T, D * T, R, NA, acc + TMX_SETUP_COL) <= g_doubles ? 1 : 0;
     }
+    // the specialised SQP shell (tmx_step.h): one thread per primary column with its waypoint's rows in registers, column pointers by
+    // TMX_STEP_CP_PASSES wave scans; the static objective pattern of the block-tridiagonal problems; no compact lists; trajopt_sco;
+    // room for the decision's copies (2 n_costs + 3 n_cnts + the log head) in the scratch of evaluate_terms behind the model values
+    const size_t eval_room = tmx_eval_scratch_doubles(R, D * T, (int)L.vel_first.size(), L.n_costs, L.n_cnts);
+    pl.step_fast = (pl.setup_fast && dpart_fits(D, T) && R >= 1 && 2 * (size_t)L.n_costs + 3 * (size_t)L.n_cnts + TMX_STEP_LOG_HEAD + 1 <= eval_room && R2 == 0 && D * T <= TMX_QP_NT && P.n_max + 1 <= TMX_STEP_CP_PASSES * TMX_QP_NT && P.flavor == 0 &&
+                    !P.st && !P.band && !P.band_rows && !E.qp_dense && !P.use_time && P.n_fx == 0 && P.n_stencil == 0 && P.n_tt == 0 && P.n_tv == 0 &&
+                    !(pl.coef_far & 2))
+                       ? 1
+                       : 0;
   }
   pl.smem_small = small_smem_bytes(L, P);
 #if TMX_IS_DEVICE
@@ -1727,6 +1736,7 @@ static tmx_status upload_tables(tmx_ctx* ctx, const Lowered& L, const Placement&
   P.coef_far = pl.coef_far;
   P.setup_fast = pl.setup_fast;
   P.polish_fast = pl.polish_fast;
+  P.step_fast = pl.step_fast;
   P.tt_place = pl.tt_place;
   P.wave_ok = pl.wave_ok;
   P.wv_gmax = pl.wv_gmax;
@@ -3282,7 +3292,8 @@ __attribute__((visibility("default"))) tmx_status tmx_debug_admm_iters(tmx_ctx* 
 }
 
 // debug hook (not in include/tmx.h): diagnostic switches of the uploaded problem (DevProblem::dbg_flags); bit 0 = scalar assembly of the
-// diagonal KKT blocks instead of the MFMA one, bit 1 = generic QP setup, bit 2 = generic polish on the dense fast path
+// diagonal KKT blocks instead of the MFMA one, bit 1 = generic QP setup, bit 2 = generic polish on the dense fast path, bit 3 = generic
+// SQP shell around the QP solve (qp_structure) on a problem the specialised one can take
 __attribute__((visibility("default"))) tmx_status tmx_debug_set_flags(tmx_ctx* ctx, int flags)
 {
   if (!ctx || !ctx->have_problem || !ctx->dp)
@@ -3310,6 +3321,15 @@ __attribute__((visibility("default"))) int tmx_debug_polish_fast(tmx_ctx* ctx)
   if (!ctx || !ctx->have_problem)
     return -1;
   return ctx->hp.polish_fast;
+}
+
+// debug hook (not in include/tmx.h): 1 when the uploaded problem qualifies for the specialised SQP shell around the QP solve
+// (DevProblem::step_fast; the kernels add the launch shape), 0 when not, -1 without a problem
+__attribute__((visibility("default"))) int tmx_debug_step_fast(tmx_ctx* ctx)
+{
+  if (!ctx || !ctx->have_problem)
+    return -1;
+  return ctx->hp.step_fast;
 }
 
 // debug hook (not in include/tmx.h): 1 = fused persistent optimize() kernel (default), 0 = one launch chain per step

@@ -2,6 +2,7 @@
 // fill the 256 CUs; problems are independent so no inter-workgroup communication exists anywhere on the path).
 #pragma once
 #include "tmx_solve.h"
+#include "tmx_step.h"
 #include "tmx_generic.h"
 
 // scratch of the term / structure kernels: dynamic LDS, or this workgroup's slice of Bt->ws_hbm for long-horizon
@@ -434,9 +435,26 @@ TMX_DEVFN void sqp_step_block(const DevProblem* P, const DevBatch* Bt, int b, do
       tp0 = tnow;
     }
 #endif
-    QpWs cwd;
-    qp_structure(P, act, coef, Bt->coef2 + (size_t)b * P->n_link * D, rhs, x, Bt->trust[b], Bt->merit + (size_t)b * P->n_cnts, Bt->dims + 4 * b,
-                 Bt->hashes + 4 * b, nullptr, reinterpret_cast<int*>(smem), tid, NT, Bt->qdyn + (size_t)b * NX, compact_lists_of(cwd, P, Bt, b));
+#if TMX_IS_DEVICE
+    // the specialised structure pass (tmx_step.h) on the problems it can take; DevProblem::dbg_flags bit 3 keeps the generic code: same bits
+    if (TMX_UNI_B(!HBM && NT == TMX_QP_NT && P->step_fast != 0 && !(P->dbg_flags & 8) && TMX_FAST_ALLOWED))
+    {
+#if TMX_ADMM_OUTLINED && TMX_STEP_OUTLINED && !(defined(TMX_PROFILE) && defined(TMX_FINE))
+      unsigned lds_off = (unsigned)(size_t)smem;  // (opaque: see the call of qp_admm_fast_nl)
+      TMX_ASM_OPAQUE_SGPR(lds_off);
+      qp_structure_fast_nl(P, Bt, b, lds_off);
+#else
+      qp_structure_fast(P, act, coef, Bt->dims + 4 * b, Bt->hashes + 4 * b, reinterpret_cast<int*>(smem), tid TMX_F5_ARGS(&tp0, Bt->prof + (size_t)b * 16));
+#endif
+    }
+    else
+#endif
+    {
+      QpWs cwd;
+      qp_structure(P, act, coef, Bt->coef2 + (size_t)b * P->n_link * D, rhs, x, Bt->trust[b], Bt->merit + (size_t)b * P->n_cnts, Bt->dims + 4 * b,
+                   Bt->hashes + 4 * b, nullptr, reinterpret_cast<int*>(smem), tid, NT, Bt->qdyn + (size_t)b * NX, compact_lists_of(cwd, P, Bt, b),
+                   nullptr, nullptr, nullptr, nullptr TMX_F5_ARGS(&tp0, Bt->prof + (size_t)b * 16));
+    }
 #if TMX_LINK_ROWS
     if (P->flavor == 1)
       sqp2_begin_qp(P, Bt, b, smem, tid, NT);
@@ -455,12 +473,31 @@ TMX_DEVFN void sqp_step_block(const DevProblem* P, const DevBatch* Bt, int b, do
     xn[v] = xq[v];
   TMX_SYNC();
   evaluate_terms(P, xn, Bt->new_cost_vals + (size_t)b * P->n_costs, Bt->new_cnt_viols + (size_t)b * P->n_cnts, smem, tid, NT);
+#if defined(TMX_PROFILE) && defined(TMX_FINE) && TMX_FINE == 5
+  [[maybe_unused]] long long* const f5_tl = &tp0;
+  [[maybe_unused]] long long* const f5_pc = Bt->prof + (size_t)b * 16;
+#endif
+  TMX_F5_TICK(13);
+#if TMX_IS_DEVICE
+  // the decision fed from LDS and the step log written by the workgroup (tmx_step.h), under the switch of the structure pass
+  if (TMX_UNI_B(!HBM && NT == TMX_QP_NT && P->step_fast != 0 && !(P->dbg_flags & 8) && TMX_FAST_ALLOWED))
+  {
+#if TMX_ADMM_OUTLINED && TMX_STEP_OUTLINED && !(defined(TMX_PROFILE) && defined(TMX_FINE))
+    unsigned lds_off = (unsigned)(size_t)smem;  // (opaque: see the call of qp_admm_fast_nl)
+    TMX_ASM_OPAQUE_SGPR(lds_off);
+    sqp_update_fast_nl(P, Bt, b, lds_off);
+#else
+    sqp_update_fast(P, Bt, b, smem, tid TMX_F5_ARGS(&tp0, Bt->prof + (size_t)b * 16));
+#endif
+  }
+  else
+#endif
 #if TMX_LINK_ROWS
   if (P->flavor == 1)
     sqp2_update_block(P, Bt, b, smem, tid, NT);
   else
 #endif
-    sqp_update_block(P, Bt, b, smem, tid, NT);
+    sqp_update_block(P, Bt, b, smem, tid, NT TMX_F5_ARGS(&tp0, Bt->prof + (size_t)b * 16));
   TMX_SYNC();
 #ifdef TMX_PROFILE
   if (tid == 0)

@@ -19,6 +19,29 @@
 #include "tmx_qp.h"
 
 #if TMX_IS_DEVICE
+// Exclusive prefix over the workgroup (TMX_QP_NT threads, thread order) of a per-thread count below 8: inside the wave by ballots of
+// the count's three bits, then the totals of the waves below through `scan` (one int per wave).  Integers - any order is exact.
+// Starts with a barrier (the last readers of `scan` are past it) and ends after the one that publishes the wave totals.
+TMX_DEVFN int block_excl_count8(int cnt, int* scan, int tid)
+{
+  const int lane = tid & 63, wave = tid >> 6;
+  const unsigned long long below = (1ull << lane) - 1ull;
+  int off = 0, tot = 0;
+  for (int bit = 0; bit < 3; ++bit)
+  {
+    const unsigned long long mk = __builtin_amdgcn_ballot_w64(((cnt >> bit) & 1) != 0);
+    off += __builtin_popcountll(mk & below) << bit;
+    tot += __builtin_popcountll(mk) << bit;
+  }
+  TMX_SYNC();
+  if (lane == 0)
+    scan[wave] = tot;
+  TMX_SYNC();
+  for (int u = 0; u < wave; ++u)
+    off += scan[u];
+  return off;
+}
+
 struct SetupRow
 {
   int r, t, na, ao, epos;

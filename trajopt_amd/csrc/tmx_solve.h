@@ -12,6 +12,28 @@
 #define TMX_ATOMIC_ADD_U64(ptr, v) __atomic_fetch_add((unsigned long long*)(ptr), (unsigned long long)(v), __ATOMIC_RELAXED)
 #endif
 
+// (-DTMX_PROFILE -DTMX_FINE=5: the SQP shell around the QP solve split - "eval+update" (slot 12) into exact evaluation 13, model values
+//  14, decision + step log + accepted copy stay in 12; "qp_structure" (slot 11) into prefix counts + column counts + column pointers 15,
+//  the hashing walks of A 6, the hashes of P and the reduction stay in 11 - tools/prof_phases.py.  Thread 0's clock, as all phase slots.)
+#if defined(TMX_PROFILE) && defined(TMX_FINE) && TMX_FINE == 5
+#define TMX_F5_PARAMS , long long *f5_tl = nullptr, long long *f5_pc = nullptr
+#define TMX_F5_ARGS(tl, pc) , (tl), (pc)
+#define TMX_F5_TICK(slot)                                                                                             \
+  do                                                                                                                  \
+  {                                                                                                                   \
+    if (tid == 0 && f5_pc != nullptr)                                                                                 \
+    {                                                                                                                 \
+      const long long now_ = TMX_CLK();                                                                               \
+      f5_pc[slot] += now_ - *f5_tl;                                                                                   \
+      *f5_tl = now_;                                                                                                  \
+    }                                                                                                                 \
+  } while (0)
+#else
+#define TMX_F5_PARAMS
+#define TMX_F5_ARGS(tl, pc)
+#define TMX_F5_TICK(slot) ((void)0)
+#endif
+
 // objective coefficient of the aux (slack) variable(s) of row r:
 //   trajopt_sco : cost rows slot_objc, constraint rows their merit coefficient (cntsToCosts, optimizers.cpp:59-81)
 //   trajopt_sqp : merit_coeff * coefficient of the set, merit_coeff = 1 for the penalty cost sets (trajopt_qp_problem.cpp:771-798)
@@ -136,7 +158,7 @@ template <bool ST = false>
 TMX_DEVFN void qp_structure(const DevProblem* P, const int* active, const double* coef, const double* coef2, const double* rhs,
                             const double* xcur, double trust, const double* merit, int* dims, unsigned long long* hashes,
                             const CscOut* out, int* iscratch, int tid, int NT, const double* qdyn = nullptr, QpWs* cw = nullptr,
-                            const double* fxH = nullptr, const double* fxg = nullptr, const double* tv_aff = nullptr, const double* tt_aff = nullptr)
+                            const double* fxH = nullptr, const double* fxg = nullptr, const double* tv_aff = nullptr, const double* tt_aff = nullptr TMX_F5_PARAMS)
 {
   (void)coef2;
   (void)fxH;
@@ -273,6 +295,7 @@ TMX_DEVFN void qp_structure(const DevProblem* P, const int* active, const double
     }
   }
   TMX_SYNC();
+  TMX_F5_TICK(15);
   const int nnzA = dims[3];
   // hashes of A: colptr (salt 3) + rowidx (salt 4); prefix hashes for the weak memcmp
   unsigned long long hA = 0ULL, wsA = 0ULL;
@@ -467,6 +490,7 @@ TMX_DEVFN void qp_structure(const DevProblem* P, const int* active, const double
         }
       }
   }
+  TMX_F5_TICK(6);
   // P: static pattern over the primary vars (upper triangle): (v-D, v) if po != 0 ; (v, v) if pd != 0
   unsigned long long hP = 0ULL, wsP = 0ULL;
   bool p_done = false;
@@ -1710,23 +1734,8 @@ TMX_DEVFN void qp_solve_block(const DevProblem* P, const DevBatch* Bt, int b, do
 #if TMX_IS_DEVICE
       if (fast_setup)
       {
-        // exclusive prefix inside the wave by ballots of the count's bits (C <= 2 slots with at most two slack variables each: the count
-        // is below 8), then the totals of the waves below; integers - any order is exact
-        const int lane = tid & 63, wave = tid >> 6;
-        const unsigned long long below = (1ull << lane) - 1ull;
-        int tot = 0;
-        for (int bit = 0; bit < 3; ++bit)
-        {
-          const unsigned long long mk = __builtin_amdgcn_ballot_w64(((cnt >> bit) & 1) != 0);
-          off += __builtin_popcountll(mk & below) << bit;
-          tot += __builtin_popcountll(mk) << bit;
-        }
-        TMX_SYNC();
-        if (lane == 0)
-          scan[wave] = tot;
-        TMX_SYNC();
-        for (int u = 0; u < wave; ++u)
-          off += scan[u];
+        // (C <= 2 slots with at most two slack variables each: the count is below 8)
+        off = block_excl_count8(cnt, scan, tid);
       }
       else
 #endif
@@ -2931,7 +2940,7 @@ TMX_DEVFN void sqp_model_values(const DevProblem* P, const DevBatch* Bt, int b, 
 
 TMX_DEVFN void sqp_decide(const DevProblem* P, const DevBatch* Bt, int b, const double* model_cost, const double* model_viol);
 template <bool ST = false>
-TMX_DEVFN void sqp_update_block(const DevProblem* P, const DevBatch* Bt, int b, double* smem, int tid, int NT)
+TMX_DEVFN void sqp_update_block(const DevProblem* P, const DevBatch* Bt, int b, double* smem, int tid, int NT TMX_F5_PARAMS)
 {
   const int NX = P->NX;
   double* model_cost = smem;                   // n_costs
@@ -2944,6 +2953,7 @@ TMX_DEVFN void sqp_update_block(const DevProblem* P, const DevBatch* Bt, int b, 
   const bool solved = Bt->cvx[b] == TMX_CVX_SOLVED && Bt->phase[b] != PHASE_DONE;
   if (solved)
     sqp_model_values<ST>(P, Bt, b, Bt->xq + (size_t)b * P->n_max, smem, tid, NT);
+  TMX_F5_TICK(14);
   // the decisions are serial per problem (O(terms)): thread 0; an accepted point is then copied by the whole workgroup
   if (tid == 0)
   {
@@ -2967,14 +2977,45 @@ TMX_DEVFN void sqp_update_block(const DevProblem* P, const DevBatch* Bt, int b, 
 // thread 0: BasicTrustRegionSQPResults::update's merits and the trust-region / penalty decisions (optimizers.cpp:380-426, 810-968).
 // An accepted step only raises Bt->accept_flag: the copy of (new_x, new costs, new violations) is done by the caller in parallel,
 // and this function reads the accepted values through cur_cost / cur_viol.
+// Where the decision reads the five per-problem vectors from and where its step log goes: the arrays of the batch and Bt->step_log
+// (head == nullptr: the generic code), or copies of the vectors in LDS and a head record of TMX_STEP_LOG_HEAD + 1 doubles that the
+// workgroup writes out afterwards together with the vectors (tmx_step.h; head[TMX_STEP_LOG_HEAD] = 0 no log, 1 head only, 2 with the
+// vectors).  Same values, same operations, same order either way.
+struct DecideIo
+{
+  const double *cost_vals, *cnt_viols, *new_cost, *new_viol, *merit;
+  double* head;
+};
+TMX_DEVFN void sqp_decide_io(const DevProblem* P, const DevBatch* Bt, int b, const double* model_cost, const double* model_viol, const DecideIo& io);
 TMX_DEVFN void sqp_decide(const DevProblem* P, const DevBatch* Bt, int b, const double* model_cost, const double* model_viol)
 {
+  const DecideIo io = { Bt->cost_vals + (size_t)b * P->n_costs,     Bt->cnt_viols + (size_t)b * P->n_cnts, Bt->new_cost_vals + (size_t)b * P->n_costs,
+                        Bt->new_cnt_viols + (size_t)b * P->n_cnts, Bt->merit + (size_t)b * P->n_cnts,     nullptr };
+  sqp_decide_io(P, Bt, b, model_cost, model_viol, io);
+}
+TMX_DEVFN void sqp_decide_io(const DevProblem* P, const DevBatch* Bt, int b, const double* model_cost, const double* model_viol, const DecideIo& io)
+{
   const tmx_sqp_params& sp = P->sqp;
-  const double* cost_vals = Bt->cost_vals + (size_t)b * P->n_costs;
-  const double* cnt_viols = Bt->cnt_viols + (size_t)b * P->n_cnts;
-  const double* new_cost = Bt->new_cost_vals + (size_t)b * P->n_costs;
-  const double* new_viol = Bt->new_cnt_viols + (size_t)b * P->n_cnts;
+  const double* cost_vals = io.cost_vals;
+  const double* cnt_viols = io.cnt_viols;
+  const double* new_cost = io.new_cost;
+  const double* new_viol = io.new_viol;
+  const double* merit_rd = io.merit;
   double* merit = Bt->merit + (size_t)b * P->n_cnts;
+  auto log_head = [&](int valid, double box_, double old_merit, double model_merit, double new_merit, double approx, double exact, double ratio) {
+    double* h = io.head;
+    h[0] = (double)Bt->merit_inc[b];
+    h[1] = (double)Bt->iter[b];
+    h[2] = box_;
+    h[3] = old_merit;
+    h[4] = model_merit;
+    h[5] = new_merit;
+    h[6] = approx;
+    h[7] = exact;
+    h[8] = ratio;
+    h[9] = (double)valid;
+    h[TMX_STEP_LOG_HEAD] = valid ? 2.0 : 1.0;
+  };
   const double* cur_cost = cost_vals;  // results_.cost_vals / cnt_viols as the decisions below see them
   const double* cur_viol = cnt_viols;
   int phase = Bt->phase[b];
@@ -2992,7 +3033,10 @@ TMX_DEVFN void sqp_decide(const DevProblem* P, const DevBatch* Bt, int b, const 
   Bt->n_qp[b] += 1;
   if (Bt->cvx[b] != TMX_CVX_SOLVED)
   {
-    step_log_write(P, Bt, b, 0, box, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0);
+    if (io.head != nullptr)
+      log_head(0, box, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0);
+    else
+      step_log_write(P, Bt, b, 0, box, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0);
     if (Bt->qp_fail[b] < sp.max_qp_solver_failures - 1)
     {
       box *= sp.trust_shrink_ratio;
@@ -3023,9 +3067,9 @@ TMX_DEVFN void sqp_decide(const DevProblem* P, const DevBatch* Bt, int b, const 
     double d0 = 0.0, d1 = 0.0, d2 = 0.0;
     for (int k = 0; k < P->n_cnts; ++k)
     {
-      d0 += cnt_viols[k] * merit[k];
-      d1 += model_viol[k] * merit[k];
-      d2 += new_viol[k] * merit[k];
+      d0 += cnt_viols[k] * merit_rd[k];
+      d1 += model_viol[k] * merit_rd[k];
+      d2 += new_viol[k] * merit_rd[k];
     }
     old_merit += d0;
     model_merit += d1;
@@ -3034,8 +3078,11 @@ TMX_DEVFN void sqp_decide(const DevProblem* P, const DevBatch* Bt, int b, const 
     const double exact = old_merit - new_merit;
     const double ratio = exact / approx;
     Bt->n_fe[b] += 1;
-    step_log_write(P, Bt, b, 1, box, cost_vals, model_cost, new_cost, cnt_viols, model_viol, new_viol, merit, old_merit, model_merit, new_merit,
-                   approx, exact, ratio);
+    if (io.head != nullptr)
+      log_head(1, box, old_merit, model_merit, new_merit, approx, exact, ratio);
+    else
+      step_log_write(P, Bt, b, 1, box, cost_vals, model_cost, new_cost, cnt_viols, model_viol, new_viol, merit_rd, old_merit, model_merit, new_merit,
+                     approx, exact, ratio);
     if (approx < sp.min_approx_improve)
     {
       retval = TMX_OPT_CONVERGED;
@@ -3107,11 +3154,11 @@ TMX_DEVFN void sqp_decide(const DevProblem* P, const DevBatch* Bt, int b, const 
       {
         for (int k = 0; k < P->n_cnts; ++k)
           if (cur_viol[k] > sp.cnt_tolerance)
-            merit[k] *= sp.merit_coeff_increase_ratio;
+            merit[k] = merit_rd[k] * sp.merit_coeff_increase_ratio;
       }
       else
         for (int k = 0; k < P->n_cnts; ++k)
-          merit[k] *= sp.merit_coeff_increase_ratio;
+          merit[k] = merit_rd[k] * sp.merit_coeff_increase_ratio;
       box = fmax(box, sp.min_trust_box_size / sp.trust_shrink_ratio * 1.5);
       Bt->merit_inc[b] += 1;
       if ((double)Bt->merit_inc[b] < sp.max_merit_coeff_increases)

@@ -153,7 +153,8 @@ struct DevProblem
   // diagnostic switches (tmx_debug_set_flags, not part of include/tmx.h): bit 0 = the D x D diagonal blocks of the reduced KKT matrix by
   // the scalar list-order loop instead of v_mfma_f64_16x16x4_f64 (tests/test_gpu_parity.py compares the two on the same QP);
   // bit 1 = the generic load and Ruiz scaling of the QP setup on a problem of the dense fast path (setup_fast below);
-  // bit 2 = the generic polish on such a problem (polish_fast below)
+  // bit 2 = the generic polish on such a problem (polish_fast below);
+  // bit 3 = the generic SQP shell around the QP solve (qp_structure) on a problem the specialised one can take (step_fast below)
   int dbg_flags;
   // TotalTime terms ON THE BLOCK CHAIN (tmx_problem_upload: the only reason for the dense engine are these terms and the QP is over
   // its size limit, or TMX_TOTAL_TIME_CHAIN=1): tt_chain = n_tt (<= TMX_TT_MAX) and qp_dense = 0 - the structured QP kernels carry
@@ -177,6 +178,11 @@ struct DevProblem
   // and room for its exchange buffers in the LDS region of the (by then dead) ADMM factors.  dbg_flags bit 2 selects the generic polish
   // on such a problem (same bits; tests/test_fast_polish.py compares the two in one library).
   int polish_fast;
+  // step_fast: the specialised SQP shell around the QP solve (tmx_step.h: qp_structure_fast) can take the problem - the conditions of
+  // setup_fast, every row on one waypoint, one thread per primary variable, a static block-tridiagonal objective, no compact row lists,
+  // trajopt_sco flavour.  dbg_flags bit 3 selects the generic code on such a problem (same bits; tests/test_fast_step.py compares the
+  // two in one library).
+  int step_fast;
 };
 TMX_HOSTDEVFN int slot_is_diff(int kind) { return kind == SLOT_JOINTVEL || kind == SLOT_JOINTVEL_INEQ; }
 #define TMX_TV_REC 5  // DevBatch::tv_aff record of one segment: cleaned Jacobian entries on x[t][j], x[t+1][j], tau[t+1] (upper row), constants of the upper / lower row

@@ -291,6 +291,10 @@ int orc_first_qp(const tmx_problem_desc* desc, const tmx_sqp_params* sqp, const 
   // one QP was solved, otherwise re-run with a trace limit is unnecessary: exact_merit_improve<0 still shrinks.
   // To be robust we stop after the first QP by making every step "converged": min_approx_improve = +inf.
   opt.getParameters().min_approx_improve = std::numeric_limits<double>::infinity();
+  // ... and when the first Model::optimize() FAILS (OSQP_MAX_ITER_REACHED under a small max_iter), the SQP would shrink the trust box and
+  // solve again (optimizers.cpp: max_qp_solver_failures): bounds and solution below would then be those of the LAST QP next to the
+  // record of the FIRST.  No retry: the run ends with OPT_FAILED and the model keeps the first QP and the iterate OSQP stopped at.
+  opt.getParameters().max_qp_solver_failures = 0;
   opt.optimize();
   auto model = P.prob->getModel();
   const Csc& Pm = model->P_csc;

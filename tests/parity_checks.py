@@ -400,22 +400,26 @@ KKT_STAT_TOL = 1e-9   # a successful polish returns a stationary point of the La
 KKT_PRIM_TOL = 1e-4   # ... that is feasible / tight to the accuracy OSQP promises (eps_abs; delta-regularised active rows)
 
 
-def check_first_qp_solve(ctx, orc, desc, x0, x_tol=TOL_TRAJ, require_same_iters=True):
+def check_first_qp_solve(ctx, orc, desc, x0, x_tol=TOL_TRAJ, require_same_iters=True, osqp=None):
     """one cold-started Model::optimize() per problem vs the oracle's OSQP on the same QP: identical integer record
     (sizes, CSC hashes, OSQP status, iteration count, rho updates, polish status), identical polish ACTIVE SET row by row,
-    primal solution within x_tol, and - independently of the oracle - a numpy KKT certificate of the returned (x, y)."""
+    primal solution within x_tol, and - independently of the oracle - a numpy KKT certificate of the returned (x, y).
+    `osqp`: the OSQP settings the caller uploaded (None: the defaults) - the oracle solves under the same ones.  Under settings the
+    certificate is no longer independent of the oracle in every row: feasibility is held to eps_abs + eps_rel |Ax| of the given settings
+    (1e-2-scale under eps = 1e-2), and with polish_refine_iter < 3 or delta > 1e-6 the device's residuals are held to twice those of the
+    oracle's own polished point, whose certificate is then measured, not asserted.  With osqp=None nothing of this applies."""
     ctx.convexify()
     xq, cvx, rec = ctx.qp_solve()
     flags = ctx.qp_active_set()
     yq = ctx.qp_duals()
     out = []
     for b in range(x0.shape[0]):
-        q = orc.first_qp(desc, x0[b])
+        q = orc.first_qp(desc, x0[b], osqp=osqp)
         r, o = rec[b], q["rec"]
         assert (r.n, r.m, r.nnzP, r.hashP, r.nnzA, r.hashA) == (o.n, o.m, o.nnzP, o.hashP, o.nnzA, o.hashA), "QP structure differs"
         assert r.warm_started == o.warm_started == 0
         assert r.osqp_status == o.osqp_status
-        oa = orc.qp_solve(q)["active"]
+        oa = orc.qp_solve(q, osqp=osqp)["active"]
         same = (r.osqp_iter, r.rho_updates, r.polish_status) == (o.osqp_iter, o.rho_updates, o.polish_status)
         same_act = bool(np.array_equal(flags[b, :r.m], oa[:r.m]))
         assert same_act == (r.hash_active == o.hash_active)
@@ -434,12 +438,27 @@ def check_first_qp_solve(ctx, orc, desc, x0, x_tol=TOL_TRAJ, require_same_iters=
             assert dx <= x_tol, f"b={b}: QP solution differs by {dx}"
         if r.polish_status == 1:
             e = ctx.export_csc(b)
-            certs = [("device", kkt_certificate(e, xq[b, :r.n], yq[b, :r.m]))]
+            certs = [("device", e, xq[b, :r.n], yq[b, :r.m])]
             if o.polish_status == 1:   # (an unpolished ADMM iterate is a KKT point to OSQP's tolerances only)
-                certs.append(("oracle", kkt_certificate(q, q["x"], q["y"])))
-            for who, cert in certs:
-                st, pr, su = cert
-                assert st <= KKT_STAT_TOL and pr <= KKT_PRIM_TOL and su <= KKT_PRIM_TOL, \
+                certs.append(("oracle", q, q["x"], q["y"]))
+            stat_tol, prim_tol = KKT_STAT_TOL, KKT_PRIM_TOL
+            if osqp is not None:
+                # under the caller's settings: OSQP accepts a polish whose residuals are below the ADMM iterate's, and those are bounded
+                # by eps_abs + eps_rel max(|Ax|, |z|) (unscaled: scaled_termination = 0) - what KKT_PRIM_TOL is for the default eps
+                prim_tol = max(prim_tol, osqp.eps_abs + osqp.eps_rel * float(np.abs(csc_dense_ops(e)[1] @ xq[b, :r.n]).max(initial=0.0)))
+                if (osqp.polish_refine_iter < 3 or osqp.delta > 1e-6) and o.polish_status == 1:
+                    # the polish solves the REGULARISED system (P + delta I) x + q + A'y = 0, A_act x - delta y = b in the SCALED variables; the
+                    # refinement passes remove the delta terms, each by a factor that grows with delta.  With fewer than the default three, or
+                    # a larger delta (1e-4, three passes, config 2 at 65 waypoints: 3.3e-6 on the oracle and on the device), the point is
+                    # stationary to a multiple of delta |D^-2 x| / c only, with the Ruiz factors D, c that no caller sees: the yardstick is the
+                    # oracle's own polished point under the same settings (twice its residuals on top of the tolerances), and the oracle's
+                    # certificate is measured, not asserted
+                    so, po, suo = kkt_certificate(q, q["x"], q["y"])
+                    stat_tol, prim_tol = stat_tol + 2.0 * so, prim_tol + 2.0 * max(po, suo)
+                    certs = certs[:1]
+            for who, qp, xc, yc in certs:
+                st, pr, su = kkt_certificate(qp, xc, yc)
+                assert st <= stat_tol and pr <= prim_tol and su <= prim_tol, \
                     f"b={b}: {who} solution is not a KKT point: stationarity {st:.2e} primal {pr:.2e} support {su:.2e}"
         out.append((same and same_act, dx))
     return out
@@ -461,7 +480,7 @@ def compare_active_sets(dev_flags, dev_y, orc_flags, orc_y):
     return False, bool(ties.all())
 
 
-def sqp_history_classes(ctx, orc, desc, x0, max_qp=128, detail=None, trace=None):
+def sqp_history_classes(ctx, orc, desc, x0, max_qp=128, detail=None, trace=None, osqp=None):
     """Whole SQP runs compared QP by QP.  The device batch is stepped one trust-region evaluation per launch and after
     every step the integer record, the polish active set and the duals of every problem are read back; the oracle returns
     the same per QP.  Per seed the result is one of
@@ -489,6 +508,7 @@ def sqp_history_classes(ctx, orc, desc, x0, max_qp=128, detail=None, trace=None)
                    about as many as the oracle shows against its own FMA build (oracle_self_classes);
       "other":     anything else (a structural / warm-start / run-length difference without any rho drift, a non-degenerate active-set
                    difference at equal rho): a failure.
+    `osqp`: the OSQP settings the caller uploaded (None: the defaults) - the oracle runs under the same ones.
     Returns (classes, dx, results)."""
     B = x0.shape[0]
     # the oracle side of every seed (two serial runs each) first, on a thread pool: ctypes releases the GIL
@@ -496,7 +516,8 @@ def sqp_history_classes(ctx, orc, desc, x0, max_qp=128, detail=None, trace=None)
     import os as _os
 
     def _oracle(b):
-        return (orc.sqp_active_sets(desc, x0[b], ctx.m_max, max_qp=max_qp), orc.sqp_batch(desc, x0[b:b + 1], max_records=max_qp, nthreads=1))
+        return (orc.sqp_active_sets(desc, x0[b], ctx.m_max, osqp=osqp, max_qp=max_qp),
+                orc.sqp_batch(desc, x0[b:b + 1], osqp=osqp, max_records=max_qp, nthreads=1))
     ctx.set_x0(x0)
     with ThreadPoolExecutor(max_workers=min(16, _os.cpu_count() or 1)) as ex:
         oracle_runs = list(ex.map(_oracle, range(B)))
@@ -660,7 +681,7 @@ def sqp_history_classes(ctx, orc, desc, x0, max_qp=128, detail=None, trace=None)
             if dt_col > 1e-3 and cls in ("identical", "tie"):
                 # the yardstick before the verdict (fuzz case 111/69 of `r4 lvs links`, host build: identical history, joints 1.3e-6 and time
                 # column 1.4e-3 from the oracle - which ends 1.3e-6 / 2.0e-3 from ITS OWN FMA build on that seed)
-                f = orc.variant("fma").sqp_batch(desc, x0[b:b + 1], nthreads=1)
+                f = orc.variant("fma").sqp_batch(desc, x0[b:b + 1], osqp=osqp, nthreads=1)
                 dself = float(np.abs(ob["x"][0] - f["x"][0])[:, desc.n_dof:].max())
                 assert dt_col <= 4.0 * dself, f"time column of an identical history differs by {dt_col} (the oracle against its FMA build: {dself})"
             dj = dj[:, :desc.n_dof]
@@ -668,12 +689,12 @@ def sqp_history_classes(ctx, orc, desc, x0, max_qp=128, detail=None, trace=None)
     return classes, np.array(dxs), res
 
 
-def oracle_self_classes(orc, orc_fma, desc, x0, max_qp=128):
+def oracle_self_classes(orc, orc_fma, desc, x0, max_qp=128, osqp=None):
     """The yardstick of the statistical classes: the oracle against ITS OWN FMA build on the same seeds, classified by the integer
     records alone with the rules of sqp_history_classes ("identical" | "admm" | "csc-noise" | "drift": no active sets here, so a
     polish tie counts as identical and an active-set difference shows at the next record it changes)."""
-    a = orc.sqp_batch(desc, x0, max_records=max_qp)
-    f = orc_fma.sqp_batch(desc, x0, max_records=max_qp)
+    a = orc.sqp_batch(desc, x0, osqp=osqp, max_records=max_qp)
+    f = orc_fma.sqp_batch(desc, x0, osqp=osqp, max_records=max_qp)
     out = []
     struct = lambda t: (t.n, t.m, t.nnzP, t.hashP)
     admm = lambda t: (t.osqp_status, t.osqp_iter, t.rho_updates, t.polish_status)

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import parity_checks as pc
+from test_simt_emulation import simt, simt_lib  # noqa: F401  (fixtures)
 from trajopt_amd import abi, configs, runtime
 
 
@@ -147,6 +148,131 @@ def test_entry_points_refuse_while_a_launch_is_pending(hostemu_lib):
     assert ctx.wait() == 0
     r = ctx.results()
     assert (r["status"] == abi.OPT_CONVERGED).all()
+    ctx.close()
+
+
+# ---- edge QPs and non-default settings ---------------------------------------------------------------------------------------------
+def _csc(n, P, q, A, l, u):
+    """dense P (its upper triangle is kept), A -> the CSC dict of tmx_qp_solve_batched; zeros of P / A are not stored"""
+    import scipy.sparse as sp
+    Pu = sp.csc_matrix(np.triu(np.asarray(P, dtype=np.float64).reshape(n, n)))
+    A = sp.csc_matrix(np.asarray(A, dtype=np.float64).reshape(-1, n))
+    Pu.sort_indices()
+    A.sort_indices()
+    return dict(n=n, m=A.shape[0], P_p=Pu.indptr.astype(np.int64), P_i=Pu.indices.astype(np.int64), P_x=Pu.data.astype(np.float64),
+                q=np.asarray(q, dtype=np.float64), A_p=A.indptr.astype(np.int64), A_i=A.indices.astype(np.int64), A_x=A.data.astype(np.float64),
+                l=np.asarray(l, dtype=np.float64), u=np.asarray(u, dtype=np.float64))
+
+
+def _settings(**kw):
+    st = abi.default_osqp_settings()
+    for k, v in kw.items():
+        assert hasattr(st, k)
+        setattr(st, k, v)
+    return st
+
+
+INF = 1e30
+EDGE_SETTINGS = [dict(scaling=0), dict(scaling=1), dict(polishing=0), dict(polish_refine_iter=0), dict(polish_refine_iter=1), dict(adaptive_rho=0),
+                 dict(adaptive_rho_interval=13), dict(check_termination=7), dict(check_termination=0, max_iter=33), dict(alpha=1.0), dict(rho=1e-3),
+                 dict(eps_abs=1e-8, eps_rel=1e-8)]
+
+
+def _edge_cases():
+    """(name, QP, settings or None, OSQP status the case aims at or None).  What the random QPs above never have: n = 1, no row at all, P = 0, a
+    zero row of A, q = 0, duplicate rows, equalities only, free rows only, sizes around the 256 threads of the kernel, fewer rows than
+    variables, the infeasibility verdicts (3: primal, 5: dual, 6: dual, inaccurate - found at max_iter) and OSQP_MAX_ITER_REACHED (7)"""
+    rng = np.random.default_rng(17)
+    M = rng.standard_normal((6, 6))
+    P6, q6 = M @ M.T + 0.1 * np.eye(6), rng.standard_normal(6)
+    G = rng.standard_normal((4, 6))
+    mid = G @ rng.standard_normal(6)
+    cases = [
+        ("n=1", _csc(1, [[2.0]], [-1.0], [[1.0]], [-0.25], [0.25]), None, 1),
+        ("m=0", _csc(3, np.diag([1.0, 2.0, 3.0]), [1.0, -1.0, 0.5], np.zeros((0, 3)), [], []), None, 1),
+        ("P=0", _csc(3, np.zeros((3, 3)), [1.0, -2.0, 0.5], np.vstack([np.eye(3), [[1.0, 1.0, 1.0]]]), [-1, -1, -1, -0.5], [1, 1, 1, 0.5]), None, 1),
+        ("zero row", _csc(6, P6, q6, np.vstack([G, np.zeros((1, 6)), np.eye(6)]), np.r_[mid - 1, -1.0, -np.ones(6) * 3], np.r_[mid + 1, 1.0, np.ones(6) * 3]), None, 1),
+        ("q=0", _csc(6, P6, np.zeros(6), np.vstack([G, np.eye(6)]), np.r_[mid - 1, -np.ones(6) * 3], np.r_[mid + 1, np.ones(6) * 3]), None, 1),
+        ("duplicate rows", _csc(6, P6, q6, np.vstack([G, G[:2], np.eye(6)]), np.r_[mid - 1, mid[:2] - 1, -np.ones(6) * 3], np.r_[mid + 1, mid[:2] + 1, np.ones(6) * 3]), None, 1),
+        ("all equality", _csc(6, P6, q6, G, mid, mid), None, 1),
+        ("all free", _csc(6, P6, q6, np.vstack([G, np.eye(6)]), -INF * np.ones(10), INF * np.ones(10)), None, 1),
+        ("m<n", _csc(6, P6, q6, G[:2], mid[:2] - 0.1, mid[:2] + 0.1), None, 1),
+        ("dual infeasible LP", _csc(2, np.zeros((2, 2)), [-1.0, 0.5], np.eye(2), [0.0, 0.0], [INF, 1.0]), None, 5),
+        ("dual infeasible QP", _csc(2, [[1.0, 0.0], [0.0, 0.0]], [0.3, -1.0], np.eye(2), [-1.0, 0.0], [1.0, INF]), None, 5),
+        ("primal infeasible QP", _csc(2, np.eye(2), [1.0, 1.0], [[1.0, 1.0], [1.0, 1.0], [1.0, 0.0]], [1.0, -INF, -5.0], [INF, 0.0, 5.0]), None, 3),
+        ("max_iter", _random_qp(np.random.default_rng(23), 9, 15), dict(max_iter=10), 7),
+    ]
+    for n in (255, 256, 257):
+        cases.append((f"n={n}", _random_qp(np.random.default_rng(n), n, n + 5), None, 1))
+    r2 = np.random.default_rng(29)
+    for k, kw in enumerate(EDGE_SETTINGS):
+        n = int(r2.integers(5, 20))
+        cases.append((f"settings {kw}", _random_qp(r2, n, n + int(r2.integers(1, 12))), kw, 7 if "max_iter" in kw else 1))
+    return cases
+
+
+# the dual-infeasible LP stopped at max_iter before the certificate holds to eps_dual_inf, but within ten times it: OSQP_DUAL_INFEASIBLE_INACCURATE
+INACCURATE = ("dual infeasible LP", dict(max_iter=23, check_termination=0))   # (status 6 for max_iter 21 .. 25, 5 from 26 on, 7 below)
+
+
+def _check_edge_cases(ctx, orc):
+    cases = _edge_cases()
+    lp = dict((c[0], c[1]) for c in cases)[INACCURATE[0]]
+    cases.append(("dual infeasible, inaccurate", lp, INACCURATE[1], 6))
+    for name, q, kw, aim in cases:
+        st = _settings(**kw) if kw else None
+        o = orc.qp_solve(q, osqp=st)
+        assert aim is None or o["status"] == aim, f"{name}: the oracle ends with status {o['status']}, the case aims at {aim}"
+        r = ctx.qp_solve_batched([q], st)[0]
+        i = r["info"]
+        assert (i.osqp_status, i.iter, i.rho_updates, i.polish_status) == (o["status"], o["iters"], o["rho_updates"], o["polish_status"]), name
+        if o["status"] in (3, 4, 5, 6):
+            assert r["cvx_status"] == abi.CVX_INFEASIBLE and np.isnan(r["x"]).all(), name
+            continue
+        assert r["cvx_status"] == (abi.CVX_SOLVED if o["status"] in (1, 2) else abi.CVX_FAILED), name
+        assert np.array_equal(r["active"], o["active"]), name
+        assert np.abs(r["x"] - o["x"]).max(initial=0.0) <= 1e-6, (name, np.abs(r["x"] - o["x"]).max())   # (x_tol of _check_batch; measured 7e-15)
+        if o["status"] not in (1, 2):
+            continue
+        # every solved case carries a KKT certificate (numpy, from the CSC arrays)
+        s_eff = st if st is not None else abi.default_osqp_settings()
+        sta, pr, su = pc.kkt_certificate(q, r["x"], r["y"])
+        P, A = pc.csc_dense_ops(q)
+        ax = A @ r["x"]
+        if i.polish_status == 1 and s_eff.polish_refine_iter >= 3:
+            # a polish with the default three passes: stationary to round-off, feasible / tight to what OSQP promises
+            stat_tol, prim_tol = 1e-8, max(pc.KKT_PRIM_TOL, s_eff.eps_abs)
+        elif i.polish_status == 1:
+            # fewer passes leave the delta terms of the regularised polish system in the residuals, scaled by Ruiz factors no caller sees
+            # (parity_checks.check_first_qp_solve): twice the residuals of the oracle's own polished point on top of the tolerances
+            so, po, suo = pc.kkt_certificate(q, o["x"], o["y"])
+            stat_tol, prim_tol = 1e-8 + 2.0 * so, max(pc.KKT_PRIM_TOL, s_eff.eps_abs) + 2.0 * max(po, suo)
+        else:
+            # an unpolished iterate that OSQP called solved passed its termination test (unscaled residuals, scaled_termination = 0):
+            # |Ax - z| < eps_abs + eps_rel max(|Ax|, |z|) with z inside the bounds (so Ax is that close to the box, and to the bound of every
+            # row with a multiplier: y_i != 0 only where z_i was clipped) and |Px + q + A'y| < eps_abs + eps_rel max(|Px|, |A'y|, |q|)
+            factor = 10.0 if o["status"] == 2 else 1.0
+            nrm = lambda v: float(np.abs(v).max(initial=0.0))
+            prim_tol = factor * (s_eff.eps_abs + s_eff.eps_rel * max(nrm(ax), nrm(np.clip(ax, q["l"], q["u"]))))
+            scale = max(1.0, nrm(q["q"]), nrm(r["y"]))   # kkt_certificate reports the stationarity residual over this scale
+            stat_tol = factor * (s_eff.eps_abs + s_eff.eps_rel * max(nrm(P @ r["x"]), nrm(A.T @ r["y"]), nrm(q["q"]))) / scale
+        assert sta <= stat_tol and pr <= prim_tol and su <= prim_tol, (name, sta, pr, su, stat_tol, prim_tol)
+
+
+def test_edge_qps_and_settings_on_host_build(hostemu_lib, orc):
+    ctx = runtime.Context(0, hostemu_lib)
+    _check_edge_cases(ctx, orc)
+    ctx.close()
+
+
+def test_edge_qps_and_settings_on_the_simt_emulation(simt, orc):
+    _check_edge_cases(simt, orc)
+
+
+@pytest.mark.gpu
+def test_edge_qps_and_settings_on_device(gpu_ctx_factory, orc):
+    ctx = gpu_ctx_factory()
+    _check_edge_cases(ctx, orc)
     ctx.close()
 
 

@@ -3332,6 +3332,37 @@ __attribute__((visibility("default"))) int tmx_debug_step_fast(tmx_ctx* ctx)
   return ctx->hp.step_fast;
 }
 
+// debug hooks (not in include/tmx.h): the engine the upload chose for the QP solves of the uploaded problem, -1 without a problem.
+// DevProblem::wave_ok (the wave-pair solver, TMX_WAVE=1), qp_dense (the dense engine), tt_chain (the number of TotalTime terms carried
+// as rank-one corrections of the block chain, 0 when not) and tv_chain (squared velocity-with-time costs on the dense-coupling chain)
+__attribute__((visibility("default"))) int tmx_debug_wave_ok(tmx_ctx* ctx)
+{
+  if (!ctx || !ctx->have_problem)
+    return -1;
+  return ctx->hp.wave_ok;
+}
+
+__attribute__((visibility("default"))) int tmx_debug_qp_dense(tmx_ctx* ctx)
+{
+  if (!ctx || !ctx->have_problem)
+    return -1;
+  return ctx->hp.qp_dense;
+}
+
+__attribute__((visibility("default"))) int tmx_debug_tt_chain(tmx_ctx* ctx)
+{
+  if (!ctx || !ctx->have_problem)
+    return -1;
+  return ctx->hp.tt_chain;
+}
+
+__attribute__((visibility("default"))) int tmx_debug_tv_chain(tmx_ctx* ctx)
+{
+  if (!ctx || !ctx->have_problem)
+    return -1;
+  return ctx->hp.tv_chain;
+}
+
 // debug hook (not in include/tmx.h): 1 = fused persistent optimize() kernel (default), 0 = one launch chain per step
 __attribute__((visibility("default"))) tmx_status tmx_debug_set_fused(tmx_ctx* ctx, int mode)
 {

@@ -259,8 +259,11 @@ TMX_DEVFN void polish_fast(const QpWs& w, const DevProblem* P, double delta, int
   TMX_SYNC();
   TMX_POLISH_TICK(7);
   // ---- the solve and its refinements; the polished iterate is (dxp, dxa | dyr, dybp, dyba)
-  for (int pass = 0; pass <= n_refine; ++pass)
+  // (with fewer than three refinement passes, two passes against the REGULARISED system first: the generic polish, tmx_solve.h)
+  const int n_reg = n_refine < 3 ? 2 : 0;
+  for (int pass = 0; pass <= n_reg + n_refine; ++pass)
   {
+    const bool reg = pass >= 1 && pass <= n_reg;
     // residual-form rhs: pass 0: r1 = -q, r2 = b ; pass > 0: r1 = -q - P x - Aact' y, r2 = b - Aact x
     double hrv[2] = { 0.0, 0.0 };
 #pragma unroll
@@ -273,6 +276,8 @@ TMX_DEVFN void polish_fast(const QpWs& w, const DevProblem* P, double delta, int
           double r2 = s.r2;
           if (pass > 0)
             r2 -= row_ax(s);
+          if (reg)
+            r2 += delta * s.dyr;
           hrv[q] = r2;
         }
 #pragma unroll
@@ -286,10 +291,14 @@ TMX_DEVFN void polish_fast(const QpWs& w, const DevProblem* P, double delta, int
               double r2 = s.r2a[k];
               if (pass > 0)
                 r2 -= s.bba[k] * s.dxa[k];
+              if (reg)
+                r2 += delta * s.dyba[k];
               gb = r2 / delta;
             }
             if (pass > 0)
               r1 -= s.sa[k] * s.dyr + s.bba[k] * s.dyba[k];
+            if (reg)
+              r1 -= delta * s.dxa[k];
             s.ta[k] = r1 + s.bba[k] * gb;
           }
       }
@@ -303,10 +312,14 @@ TMX_DEVFN void polish_fast(const QpWs& w, const DevProblem* P, double delta, int
         double r2 = r2bp;
         if (pass > 0)
           r2 -= bbp * dxp;
+        if (reg)
+          r2 += delta * dybp;
         gb = r2 / delta;
       }
       if (pass > 0)
         r1 -= p_times_x() + aty_rows() + bbp * dybp;
+      if (reg)
+        r1 -= delta * dxp;
       rhs = r1 + bbp * gb;
     }
     TMX_POLISH_TICK(7);
@@ -392,6 +405,8 @@ TMX_DEVFN void polish_fast(const QpWs& w, const DevProblem* P, double delta, int
               double r2 = s.r2a[k];
               if (pass > 0)
                 r2 -= s.bba[k] * s.dxa[k];
+              if (reg)
+                r2 += delta * s.dyba[k];
               dyb = (s.bba[k] * s.ta[k] - r2) / delta;
             }
             if (pass == 0)
@@ -420,6 +435,8 @@ TMX_DEVFN void polish_fast(const QpWs& w, const DevProblem* P, double delta, int
         double r2 = r2bp;
         if (pass > 0)
           r2 -= bbp * dxp;
+        if (reg)
+          r2 += delta * dybp;
         dyb = (bbp * tpv - r2) / delta;
       }
       if (pass == 0)

@@ -2409,8 +2409,14 @@ TMX_DEVFN void qp_solve_block(const DevProblem* P, const DevBatch* Bt, int b, do
     TMX_TICK(14);
 #endif
     // polished iterate lives in (dxp, dxa | dyr, dybp, dyba)
-    for (int pass = 0; pass <= st.polish_refine_iter; ++pass)
+    // OSQP's pass 0 is the solution of the REGULARISED system (P + delta I, A_act'; A_act, -delta I) to QDLDL's accuracy; the reduced
+    // system solved here (weights 1 / delta: condition ~ 1 / delta^2) returns it with a larger error, which the default three refinement
+    // passes absorb.  With fewer passes they do not (config 2 at 65 waypoints, polish_refine_iter = 0: dual residual 6.5e-3 where OSQP has
+    // 3.2e-5, and the polish is rejected): n_reg passes then refine against the regularised system first.  No change of any bit at >= 3.
+    const int n_reg = st.polish_refine_iter < 3 ? 2 : 0;
+    for (int pass = 0; pass <= n_reg + st.polish_refine_iter; ++pass)
     {
+      const bool reg = pass >= 1 && pass <= n_reg;
       // residual-form rhs: pass 0: r1 = -q, r2 = b ; pass > 0: r1 = -q - P x - Aact' y, r2 = b - Aact x
       TMX_ROWS(wp, r)
       {
@@ -2430,6 +2436,8 @@ TMX_DEVFN void qp_solve_block(const DevProblem* P, const DevBatch* Bt, int b, do
             for (int k = 0; k < wp.naux[r]; ++k)
               ax += wp.sa[wp.aoff[r] + k] * wp.dxa[wp.aoff[r] + k];
             r2 -= ax;
+            if (reg)
+              r2 += delta * wp.dyr[r];
           }
           g = r2;  // unscaled: kkt_solve(mode 1) applies the 1/delta weight in its cancellation-free form
         }
@@ -2445,10 +2453,14 @@ TMX_DEVFN void qp_solve_block(const DevProblem* P, const DevBatch* Bt, int b, do
           double r2 = (wp.flg_bp[v] < 0) ? wp.lbp[v] : wp.ubp[v];
           if (pass > 0)
             r2 -= wp.bbp[v] * wp.dxp[v];
+          if (reg)
+            r2 += delta * wp.dybp[v];
           gb = r2 / delta;
         }
         if (pass > 0)
           r1 -= p_times(wp, wp.dxp, v) + at_rows(wp, P, wp.dyr, v) + wp.bbp[v] * wp.dybp[v];
+        if (reg)
+          r1 -= delta * wp.dxp[v];
         wp.tp[v] = r1 + wp.bbp[v] * gb;
       }
       TMX_ROWS(wp, r)
@@ -2463,10 +2475,14 @@ TMX_DEVFN void qp_solve_block(const DevProblem* P, const DevBatch* Bt, int b, do
               double r2 = (wp.flg_ba[a] < 0) ? 0.0 : TMX_OSQP_INFTY * wp.Eba[a];
               if (pass > 0)
                 r2 -= wp.bba[a] * wp.dxa[a];
+              if (reg)
+                r2 += delta * wp.dyba[a];
               gb = r2 / delta;
             }
             if (pass > 0)
               r1 -= wp.sa[a] * wp.dyr[r] + wp.bba[a] * wp.dyba[a];
+            if (reg)
+              r1 -= delta * wp.dxa[a];
             wp.ta[a] = r1 + wp.bba[a] * gb;
           }
       TMX_SYNC();
@@ -2506,6 +2522,8 @@ TMX_DEVFN void qp_solve_block(const DevProblem* P, const DevBatch* Bt, int b, do
           double r2 = (wp.flg_bp[v] < 0) ? wp.lbp[v] : wp.ubp[v];
           if (pass > 0)
             r2 -= wp.bbp[v] * wp.dxp[v];
+          if (reg)
+            r2 += delta * wp.dybp[v];
           dyb = (wp.bbp[v] * wp.tp[v] - r2) / delta;
         }
         if (pass == 0)
@@ -2532,6 +2550,8 @@ TMX_DEVFN void qp_solve_block(const DevProblem* P, const DevBatch* Bt, int b, do
             double r2 = (wp.flg_ba[a] < 0) ? 0.0 : TMX_OSQP_INFTY * wp.Eba[a];
             if (pass > 0)
               r2 -= wp.bba[a] * wp.dxa[a];
+            if (reg)
+              r2 += delta * wp.dyba[a];
             dyb = (wp.bba[a] * wp.ta[a] - r2) / delta;
           }
           if (pass == 0)

@@ -1516,8 +1516,11 @@ TMX_DEVFN void qp_solve_wave(const DevProblem* P, const DevBatch* Bt, int b, dou
     TMX_SYNC();
     kkt_factor(wp, P, 1, delta, delta, tid, NT);
     kkt_invert_chain_wave0(wp, tid);
-    for (int pass = 0; pass <= st.polish_refine_iter; ++pass)
+    // (with fewer than three refinement passes, two passes against the REGULARISED system first: the generic polish, tmx_solve.h)
+    const int n_reg = st.polish_refine_iter < 3 ? 2 : 0;
+    for (int pass = 0; pass <= n_reg + st.polish_refine_iter; ++pass)
     {
+      const bool reg = pass >= 1 && pass <= n_reg;
       TMX_ROWS(wp, r)
       {
         double g = 0.0;
@@ -1533,6 +1536,8 @@ TMX_DEVFN void qp_solve_wave(const DevProblem* P, const DevBatch* Bt, int b, dou
             for (int k = 0; k < wp.naux[r]; ++k)
               ax += wp.sa[wp.aoff[r] + k] * wp.dxa[wp.aoff[r] + k];
             r2 -= ax;
+            if (reg)
+              r2 += delta * wp.dyr[r];
           }
           g = r2;
         }
@@ -1548,10 +1553,14 @@ TMX_DEVFN void qp_solve_wave(const DevProblem* P, const DevBatch* Bt, int b, dou
           double r2 = (wp.flg_bp[v] < 0) ? wp.lbp[v] : wp.ubp[v];
           if (pass > 0)
             r2 -= wp.bbp[v] * wp.dxp[v];
+          if (reg)
+            r2 += delta * wp.dybp[v];
           gb = r2 / delta;
         }
         if (pass > 0)
           r1 -= p_times(wp, wp.dxp, v) + at_rows(wp, P, wp.dyr, v) + wp.bbp[v] * wp.dybp[v];
+        if (reg)
+          r1 -= delta * wp.dxp[v];
         wp.tp[v] = r1 + wp.bbp[v] * gb;
       }
       TMX_ROWS(wp, r)
@@ -1566,10 +1575,14 @@ TMX_DEVFN void qp_solve_wave(const DevProblem* P, const DevBatch* Bt, int b, dou
               double r2 = (wp.flg_ba[a] < 0) ? 0.0 : TMX_OSQP_INFTY * wp.Eba[a];
               if (pass > 0)
                 r2 -= wp.bba[a] * wp.dxa[a];
+              if (reg)
+                r2 += delta * wp.dyba[a];
               gb = r2 / delta;
             }
             if (pass > 0)
               r1 -= wp.sa[a] * wp.dyr[r] + wp.bba[a] * wp.dyba[a];
+            if (reg)
+              r1 -= delta * wp.dxa[a];
             wp.ta[a] = r1 + wp.bba[a] * gb;
           }
       TMX_SYNC();
@@ -1590,6 +1603,8 @@ TMX_DEVFN void qp_solve_wave(const DevProblem* P, const DevBatch* Bt, int b, dou
           double r2 = (wp.flg_bp[v] < 0) ? wp.lbp[v] : wp.ubp[v];
           if (pass > 0)
             r2 -= wp.bbp[v] * wp.dxp[v];
+          if (reg)
+            r2 += delta * wp.dybp[v];
           dyb = (wp.bbp[v] * wp.tp[v] - r2) / delta;
         }
         if (pass == 0)
@@ -1616,6 +1631,8 @@ TMX_DEVFN void qp_solve_wave(const DevProblem* P, const DevBatch* Bt, int b, dou
             double r2 = (wp.flg_ba[a] < 0) ? 0.0 : TMX_OSQP_INFTY * wp.Eba[a];
             if (pass > 0)
               r2 -= wp.bba[a] * wp.dxa[a];
+            if (reg)
+              r2 += delta * wp.dyba[a];
             dyb = (wp.bba[a] * wp.ta[a] - r2) / delta;
           }
           if (pass == 0)

@@ -225,8 +225,8 @@ def test_cpp_reference_kats_on_host_build(hostemu_lib, inputs, orc):
 
 
 def test_cpp_two_waypoint_terms_are_refused_by_the_product_configuration(hostemu_lib_nolink, inputs):
-    """kernel sources in the product's configuration (TMX_LINK_ROWS=0): the JointVel constraint / hinge KATs end in the
-    library's explicit refusal, exactly what the GPU tier expects from libtrajopt_mi355x.so this round"""
+    """kernel sources built without pair rows (TMX_LINK_ROWS=0; the product library has built with 1 since pair rows shipped,
+    the name of the test is older): the JointVel constraint / hinge KATs end in the library's explicit refusal"""
     exe = _build(hostemu_lib_nolink, "hostemu_nolink")
     res, _, out = _run(exe, inputs["path"], "joint_vel")
     assert out.count("LINKROWS refused") == 3 and "JOINTVEL done" in out and set(res) == {"kinematic_terms"}   # + the acceleration cost of function_terms

@@ -102,8 +102,9 @@ def test_full_sqp_config3_car_seat_shape(emu, orc):
 
 
 def test_product_configuration_of_the_kernel_sources(hostemu_lib_nolink, hostemu_lib, orc):
-    """The host build used above has the two-waypoint rows compiled in; the product library has not.  Same sources with the
-    product's configuration: bit-identical results on problems without such rows, and an explicit refusal of problems with."""
+    """The host build used above has the two-waypoint rows compiled in (TMX_LINK_ROWS=1), as the product library has since pair
+    rows shipped (the name of the test is older).  Same sources built with TMX_LINK_ROWS=0: bit-identical results on problems
+    without such rows, and an explicit refusal of problems with."""
     from trajopt_amd.problem import BasicInfo, JointVelTermInfo, ProblemConstructionInfo
     for cid in (0, 1, 9, 13):
         pci, s, g = _cfg(cid) if cid != 1 else _cfg(1, T=8)

@@ -439,7 +439,7 @@ TMX_DEVFN void sqp_step_block(const DevProblem* P, const DevBatch* Bt, int b, do
     // the specialised structure pass (tmx_step.h) on the problems it can take; DevProblem::dbg_flags bit 3 keeps the generic code: same bits
     if (TMX_UNI_B(!HBM && NT == TMX_QP_NT && P->step_fast != 0 && !(P->dbg_flags & 8) && TMX_FAST_ALLOWED))
     {
-#if TMX_ADMM_OUTLINED && TMX_STEP_OUTLINED && !(defined(TMX_PROFILE) && defined(TMX_FINE))
+#if TMX_ADMM_OUTLINED && !(defined(TMX_PROFILE) && defined(TMX_FINE))
       unsigned lds_off = (unsigned)(size_t)smem;  // (opaque: see the call of qp_admm_fast_nl)
       TMX_ASM_OPAQUE_SGPR(lds_off);
       qp_structure_fast_nl(P, Bt, b, lds_off);
@@ -482,7 +482,7 @@ TMX_DEVFN void sqp_step_block(const DevProblem* P, const DevBatch* Bt, int b, do
   // the decision fed from LDS and the step log written by the workgroup (tmx_step.h), under the switch of the structure pass
   if (TMX_UNI_B(!HBM && NT == TMX_QP_NT && P->step_fast != 0 && !(P->dbg_flags & 8) && TMX_FAST_ALLOWED))
   {
-#if TMX_ADMM_OUTLINED && TMX_STEP_OUTLINED && !(defined(TMX_PROFILE) && defined(TMX_FINE))
+#if TMX_ADMM_OUTLINED && !(defined(TMX_PROFILE) && defined(TMX_FINE))
     unsigned lds_off = (unsigned)(size_t)smem;  // (opaque: see the call of qp_admm_fast_nl)
     TMX_ASM_OPAQUE_SGPR(lds_off);
     sqp_update_fast_nl(P, Bt, b, lds_off);

@@ -568,11 +568,7 @@ TMX_DEVFN double dpart_separator_row_rc(const HotLds& h, const DMap& m, const do
     r[p] = yr[p];
   }
   double s[4] = { 0.0, 0.0, 0.0, 0.0 };
-#ifndef TMX_SEP_DIFF_FIRST
-#define TMX_SEP_DIFF_FIRST 1  // 0: difference and product of a column back to back (rounds 2 - 5; same bits; A/B switch)
-#endif
-#if TMX_SEP_DIFF_FIRST
-  // all sixteen differences, THEN the products (round 6): left alone the scheduler emitted sixteen (v_add_f64 -> dependent v_fmac_f64)
+  // all sixteen differences, THEN the products: left alone the scheduler emitted sixteen (v_add_f64 -> dependent v_fmac_f64)
   // pairs through one temporary register - sixteen dependent-issue stalls in the phase every other wave waits for
   double df[2 * TMX_RC_ZP];
 #pragma unroll
@@ -589,15 +585,6 @@ TMX_DEVFN double dpart_separator_row_rc(const HotLds& h, const DMap& m, const do
     s[(2 * u) & 3] = __builtin_fma(zq[2 * p], df[2 * p], s[(2 * u) & 3]);
     s[(2 * u + 1) & 3] = __builtin_fma(zq[2 * p + 1], df[2 * p + 1], s[(2 * u + 1) & 3]);
   }
-#else
-#pragma unroll
-  for (int p = 0; p < TMX_RC_ZP; ++p)
-  {
-    const int u = p & 3;
-    s[(2 * u) & 3] = __builtin_fma(zq[2 * p], l[p].x - r[p].x, s[(2 * u) & 3]);
-    s[(2 * u + 1) & 3] = __builtin_fma(zq[2 * p + 1], l[p].y - r[p].y, s[(2 * u + 1) & 3]);
-  }
-#endif
   return quad_sum((s[0] + s[1]) + (s[2] + s[3]));
 }
 TMX_DEVFN double dpart_correct_rc(const HotLds& h, const DMap& m, double y, const double (&gr)[2 * TMX_RC_GP], const double (&gc)[8])
@@ -865,17 +852,12 @@ TMX_DEVFN void row_phase_c(RowRegsT<NA>& g, double alpha, double rho_b, double r
 // machine scheduler can pull one chain ahead of the other (and nothing can be sunk behind a branch).  Inactive rows are computed too -
 // their registers hold zeros (row_load), every product stays zero and nothing of them is stored.  Same operations in the same order
 // per row as row_phase_a / row_phase_c: bit-identical results.
-// pin(...): a stage boundary of the lock-step chains.  TMX_PIN_ASM=1 (default): the values become opaque read-write operands of ONE
-// empty volatile asm - they must all exist before it and nothing that depends on its outputs can start before it (holds against IR
-// passes and the machine scheduler alike).  0: a scheduling barrier only; 2: nothing (source order alone).  Measured same-box with the
-// s_waitcnt repair below in place: 150.1 k / 148.5 k QP solves/s (1 / 0), profiles/r06/r06j_ab5_*.
-#ifndef TMX_PIN_ASM
-#define TMX_PIN_ASM 1
-#endif
-#if TMX_IS_GCN && TMX_PIN_ASM == 1
+// pin(...): a stage boundary of the lock-step chains.  On the device the values become opaque read-write operands of ONE empty
+// volatile asm - they must all exist before it and nothing that depends on its outputs can start before it (holds against IR passes
+// and the machine scheduler alike); elsewhere it is nothing.  A scheduling barrier alone measured slower same-box, with the
+// s_waitcnt repair below in place: 150.1 k (asm) / 148.5 k (barrier) QP solves/s, profiles/r06/r06j_ab5_*.
+#if TMX_IS_GCN
 #define TMX_PIN_BODY(...) asm volatile("" : __VA_ARGS__)
-#elif TMX_IS_GCN && TMX_PIN_ASM == 0
-#define TMX_PIN_BODY(...) __builtin_amdgcn_sched_barrier(0)
 #else
 #define TMX_PIN_BODY(...) ((void)0)
 #endif
@@ -1104,9 +1086,6 @@ struct TmxTag
   static constexpr bool value = V;
 };
 #define TMX_NROW (512 / TMX_QP_NT)
-#ifndef TMX_ROWS_LOCKSTEP
-#define TMX_ROWS_LOCKSTEP 3  // lock-step phases A / C: 1 in every instantiation, 2 in the two-row ones, 3 in the two-row and the two-slack ones; 0: the row-after-row code of rounds 2 - 5 (same bits; A/B switch)
-#endif
 #if defined(TMX_PROFILE) && defined(TMX_PROFILE_LOOP) && TMX_PROFILE_LOOP != 2
 #define TMX_LTICK(s) TMX_TICK(s)
 #else
@@ -1247,13 +1226,12 @@ TMX_DEVFN int admm_burst_core(const QpWs& w, const DevProblem* P, int n_iter, bo
   // column v of A restricted to the rows of its waypoint, kept in registers (first 16 rows; a longer list falls back
   // to a loop for the remainder)
   double cj[16];
-#ifndef TMX_CJX
-#define TMX_CJX 1  // extra cached pairs beyond 16 (config 1's goal waypoint has 17 rows: 7 goal + 2 upright + 8 collision; its seven threads ran a
-                  // dependent index -> coefficient -> product loop in phase B of every iteration: + 180 cycles for their whole wave, tools/prof_loop.py)
-#endif
-  [[maybe_unused]] double cjx[TMX_CJX ? 2 * TMX_CJX : 1];
+  // extra cached pairs beyond 16 (config 1's goal waypoint has 17 rows: 7 goal + 2 upright + 8 collision; without the pair its seven threads ran a
+  // dependent index -> coefficient -> product loop in phase B of every iteration: + 180 cycles for their whole wave, tools/prof_loop.py)
+  constexpr int CJX = 1;
+  double cjx[2 * CJX];
   // entry k of the cached column (k a literal after unrolling): the first sixteen in cj, the extra pairs in cjx
-  auto cjv = [&](int k) __attribute__((always_inline)) { return k < 16 ? cj[k < 16 ? k : 0] : cjx[(TMX_CJX && k >= 16) ? k - 16 : 0]; };
+  auto cjv = [&](int k) __attribute__((always_inline)) { return k < 16 ? cj[k < 16 ? k : 0] : cjx[k >= 16 ? k - 16 : 0]; };
   int e0off = 0, q_rest = 0, q_end = 0;
   {
     const int t = vt, j = vj;
@@ -1265,17 +1243,15 @@ TMX_DEVFN int admm_burst_core(const QpWs& w, const DevProblem* P, int n_iter, bo
       const int r = ok ? w.wp_list[q0 + k] : 0;
       cj[k] = ok ? w.coef[r * D + j] : 0.0;
     }
-#if TMX_CJX
 #pragma unroll
-    for (int k = 0; k < 2 * TMX_CJX; ++k)
+    for (int k = 0; k < 2 * CJX; ++k)
     {
       const bool ok = pv && (q0 + 16 + k < q1);
       const int r = ok ? w.wp_list[q0 + 16 + k] : 0;
       cjx[k] = ok ? w.coef[r * D + j] : 0.0;
     }
-#endif
     e0off = pst(t);
-    q_rest = q0 + 16 + 2 * TMX_CJX;
+    q_rest = q0 + 16 + 2 * CJX;
     q_end = pv ? q1 : 0;
   }
   const int q0v = w.wp_start[vt];
@@ -1331,7 +1307,7 @@ TMX_DEVFN int admm_burst_core(const QpWs& w, const DevProblem* P, int n_iter, bo
   auto iteration = [&](auto keep_tag) __attribute__((always_inline)) {
     constexpr bool keep = decltype(keep_tag)::value;
     double ta[NR][NAX];
-    if constexpr (TMX_ROWS_LOCKSTEP == 1 || (TMX_ROWS_LOCKSTEP >= 2 && NR >= 2) || (TMX_ROWS_LOCKSTEP == 3 && NAX >= 2))
+    if constexpr (NR >= 2 || NAX >= 2)
     {
       double e[NR];
       rows_phase_a<NR, NAX>(g, sigma, rho_b, ta, e);
@@ -1371,16 +1347,14 @@ TMX_DEVFN int admm_burst_core(const QpWs& w, const DevProblem* P, int n_iter, bo
         a3 = __builtin_fma(cj[2 * k + 3], e2[k + 1].y, a3);
       }
       double ate = (a0 + a1) + (a2 + a3);
-#if TMX_CJX
       // same order and rounding as the remainder loop below (product, then sum)
 #pragma unroll
-      for (int k = 0; k < TMX_CJX; ++k)
+      for (int k = 0; k < CJX; ++k)
       {
         const tmx_d2 ex = ep[8 + k];
         ate += cjx[2 * k] * ex.x;
         ate += cjx[2 * k + 1] * ex.y;
       }
-#endif
       for (int q = q_rest; q < q_end; ++q)
       {
         const int r = w.wp_list[q];
@@ -1396,26 +1370,16 @@ TMX_DEVFN int admm_burst_core(const QpWs& w, const DevProblem* P, int n_iter, bo
     double yint = 0.0;
     if (INTW && interior)
     {
-#ifndef TMX_BSEP_EARLY
-#define TMX_BSEP_EARLY 1  // 0: b_sep is read inside the conditional store, after the dot (rounds 2 - 5; same bits; A/B switch)
-#endif
-#if TMX_BSEP_EARLY
       // b_sep of the separator row this thread completes: requested WITH the right-hand side of the dot product (an unconditional load
       // at a clamped index), not after it inside the conditional store - one LDS round trip less on the path the separator phase waits for
       const double bsl = RC ? bsep[wr_yl ? i_yl : 0] : 0.0;
-#endif
       if constexpr (RC && INTW)
         yint = dpart_interior_rc(h, mp, gr);
       else
         yint = dpart_interior(h, mp);
-#if TMX_BSEP_EARLY
       const double outl = RC ? bsl - cnext * yint : cnext * yint;  // RC: b_sep - C y_left in one slot
       if (wr_yl)
         h.sx[i_yl] = outl;
-#else
-      if (wr_yl)
-        h.sx[i_yl] = RC ? bsep[i_yl] - cnext * yint : cnext * yint;  // RC: b_sep - C y_left in one slot
-#endif
       if (wr_yr)
         h.sx[i_yr] = cprev * yint;
     }
@@ -1453,7 +1417,7 @@ TMX_DEVFN int admm_burst_core(const QpWs& w, const DevProblem* P, int n_iter, bo
     TMX_LTICK(4);
     // phase C
     const double xtv = h.tp[vp];
-    if constexpr (TMX_ROWS_LOCKSTEP == 1 || (TMX_ROWS_LOCKSTEP >= 2 && NR >= 2) || (TMX_ROWS_LOCKSTEP == 3 && NAX >= 2))
+    if constexpr (NR >= 2 || NAX >= 2)
     {
       // x~ of both rows' waypoints first (eight 16-byte loads in flight), then the two dots and the two chains in lock-step
       tmx_d2 x2[NR][4];
@@ -1617,10 +1581,7 @@ TMX_DEVFN int admm_burst_core(const QpWs& w, const DevProblem* P, int n_iter, bo
   // primary variable: seven fast_rcp (a load, v_rcp_f64 and four dependent FMAs each) that stood one after the other inside the
   // per-row regions, recomputed by certs8.  Formed here ONCE per check, all loads first and the Newton steps of all of them stage by
   // stage (lock-step), then read from registers.  Same function on the same operands: same bits.
-#ifndef TMX_CHECK_RCP_BATCH
-#define TMX_CHECK_RCP_BATCH 1  // 0: fast_rcp where the quotient is used (rounds 2 - 6a; same bits; A/B switch)
-#endif
-  [[maybe_unused]] double rc_er[NR], rc_eba[NR][NAX], rc_da[NR][NAX], rc_pv[2];
+  double rc_er[NR], rc_eba[NR][NAX], rc_da[NR][NAX], rc_pv[2];
   auto check_rcps = [&]() __attribute__((always_inline)) {
     double x_er[NR], x_eba[NR][NAX], x_da[NR][NAX], x_pv[2];
 #pragma unroll
@@ -1698,7 +1659,6 @@ TMX_DEVFN int admm_burst_core(const QpWs& w, const DevProblem* P, int n_iter, bo
       const RowRegsT<NAX>& gq = g[q];
       if (gq.act)
       {
-        const int r = rowi[q];
         double xb[8];
         {
           const tmx_lds_d2* xb2 = reinterpret_cast<const tmx_lds_d2*>(h.tp + tb[q]);
@@ -1720,7 +1680,7 @@ TMX_DEVFN int admm_burst_core(const QpWs& w, const DevProblem* P, int n_iter, bo
           if (k < gq.na)
             ax = ax + gq.sa[k] * gq.xa[k];
         {
-          const double z = gq.z, einv = TMX_CHECK_RCP_BATCH ? rc_er[q] : fast_rcp(w.Er[r]);
+          const double z = gq.z, einv = rc_er[q];
           m[0] = fmax(m[0], fabs(einv * (ax - z)));
           m[1] = fmax(m[1], fabs(ax - z));
           m[2] = fmax(m[2], fabs(z));
@@ -1732,8 +1692,7 @@ TMX_DEVFN int admm_burst_core(const QpWs& w, const DevProblem* P, int n_iter, bo
         for (int k = 0; k < NAX; ++k)
           if (k < gq.na)
           {
-            const int a = w.aoff[r] + k;
-            const double axa = gq.bb[k] * gq.xa[k], z = gq.za[k], einv = TMX_CHECK_RCP_BATCH ? rc_eba[q][k] : fast_rcp(w.Eba[a]);
+            const double axa = gq.bb[k] * gq.xa[k], z = gq.za[k], einv = rc_eba[q][k];
             m[0] = fmax(m[0], fabs(einv * (axa - z)));
             m[1] = fmax(m[1], fabs(axa - z));
             m[2] = fmax(m[2], fabs(z));
@@ -1742,7 +1701,7 @@ TMX_DEVFN int admm_burst_core(const QpWs& w, const DevProblem* P, int n_iter, bo
             m[5] = fmax(m[5], fabs(einv * axa));
             const double aty = gq.sa[k] * gq.y + gq.bb[k] * gq.ya[k];
             const double res = gq.qa[k] + aty;
-            const double dinv = TMX_CHECK_RCP_BATCH ? rc_da[q][k] : fast_rcp(w.Da[a]);
+            const double dinv = rc_da[q][k];
             m[6] = fmax(m[6], fabs(dinv * res));
             m[7] = fmax(m[7], fabs(res));
             m[8] = fmax(m[8], fabs(gq.qa[k]));
@@ -1755,7 +1714,7 @@ TMX_DEVFN int admm_burst_core(const QpWs& w, const DevProblem* P, int n_iter, bo
     if (pv)
     {
       {
-        const double ax = bb * xp, z = zb, einv = TMX_CHECK_RCP_BATCH ? rc_pv[0] : fast_rcp(w.Ebp[v]);
+        const double ax = bb * xp, z = zb, einv = rc_pv[0];
         m[0] = fmax(m[0], fabs(einv * (ax - z)));
         m[1] = fmax(m[1], fabs(ax - z));
         m[2] = fmax(m[2], fabs(z));
@@ -1775,7 +1734,7 @@ TMX_DEVFN int admm_burst_core(const QpWs& w, const DevProblem* P, int n_iter, bo
       {
         const tmx_lds_d2* ep = reinterpret_cast<const tmx_lds_d2*>(h.hr + e0off);
   #pragma unroll
-        for (int k2 = 0; k2 < 8 + TMX_CJX; ++k2)
+        for (int k2 = 0; k2 < 8 + CJX; ++k2)
         {
           const tmx_d2 e2 = ep[k2];
           const double p0 = cjv(2 * k2) * e2.x, p1 = cjv(2 * k2 + 1) * e2.y;
@@ -1814,7 +1773,7 @@ TMX_DEVFN int admm_burst_core(const QpWs& w, const DevProblem* P, int n_iter, bo
       }
       const double aty = ((s0 + s1) + (s2 + s3)) + bb * yb;
       const double res = (qv + px) + aty;
-      const double dinv = TMX_CHECK_RCP_BATCH ? rc_pv[1] : fast_rcp(w.Dp[v]);
+      const double dinv = rc_pv[1];
       m[6] = fmax(m[6], fabs(dinv * res));
       m[7] = fmax(m[7], fabs(res));
       m[8] = fmax(m[8], fabs(qv));
@@ -1884,7 +1843,7 @@ TMX_DEVFN int admm_burst_core(const QpWs& w, const DevProblem* P, int n_iter, bo
             const int a = w.aoff[r] + k;
             const double da = kp_dya[q][k];
             m[14] = fmax(m[14], fabs(w.Eba[a] * da));
-            const double dinv = TMX_CHECK_RCP_BATCH ? rc_da[q][k] : fast_rcp(w.Da[a]);
+            const double dinv = rc_da[q][k];
             m[15] = fmax(m[15], fabs((gq.sa[k] * dy + gq.bb[k] * da) * dinv));
             m[16] = fmax(m[16], fabs(w.Da[a] * kd_dxa[q][k]));
           }
@@ -1900,7 +1859,7 @@ TMX_DEVFN int admm_burst_core(const QpWs& w, const DevProblem* P, int n_iter, bo
       {
         const tmx_lds_d2* ep = reinterpret_cast<const tmx_lds_d2*>(h.sx + e0off);
 #pragma unroll
-        for (int k2 = 0; k2 < 8 + TMX_CJX; ++k2)
+        for (int k2 = 0; k2 < 8 + CJX; ++k2)
         {
           const tmx_d2 e2 = ep[k2];
           s0 = __builtin_fma(cjv(2 * k2), e2.x, s0);
@@ -1909,7 +1868,7 @@ TMX_DEVFN int admm_burst_core(const QpWs& w, const DevProblem* P, int n_iter, bo
       }
       for (int q = q_rest; q < q_end; ++q)
         s0 += w.coef[w.wp_list[q] * D + vj] * h.sx[e0off + (q - q0v)];
-      const double dinv = TMX_CHECK_RCP_BATCH ? rc_pv[1] : fast_rcp(w.Dp[v]);
+      const double dinv = rc_pv[1];
       m[15] = fmax(m[15], fabs(((s0 + s1) + bb * dy) * dinv));
       m[16] = fmax(m[16], fabs(w.Dp[v] * kd_dxp));
       double px = w.pd[v] * kd_dxp;
@@ -1951,8 +1910,7 @@ TMX_DEVFN int admm_burst_core(const QpWs& w, const DevProblem* P, int n_iter, bo
 #pragma unroll
       for (int k = 0; k < 22; ++k)
         m[k] = 0.0;
-      if (TMX_CHECK_RCP_BATCH)
-        check_rcps();
+      check_rcps();
       norms14(m);
       double m14[14];
 #pragma unroll
@@ -2002,8 +1960,7 @@ TMX_DEVFN int admm_burst_core(const QpWs& w, const DevProblem* P, int n_iter, bo
 #pragma unroll
     for (int k = 0; k < 22; ++k)
       m[k] = 0.0;
-    if (TMX_CHECK_RCP_BATCH)
-      check_rcps();
+    check_rcps();
     norms14(m);
 #if defined(TMX_FINE) && TMX_FINE == 2
     TMX_TICK(14);
@@ -2017,18 +1974,10 @@ TMX_DEVFN int admm_burst_core(const QpWs& w, const DevProblem* P, int n_iter, bo
 #pragma unroll
     for (int k = 0; k < 18; ++k)
       m18[k] = m[k];
-    [[maybe_unused]] const bool sall[18] = { false, false, false, false, false, false, false, false, false, false, false, false, false, false, false, false, false, false };
-#ifndef TMX_CHECK_REDUCE_ROWS
-#define TMX_CHECK_REDUCE_ROWS 1  // 0: the value-by-value block_reduce of rounds 2 - 5 (same bits; A/B switch)
-#endif
-#if TMX_CHECK_REDUCE_ROWS
     static_assert(TMX_QP_NT == 256, "block_max_rows: 16 rows of 16 lanes");
     // scratch: the partials in sx (read by certs8 before the routine's first barrier, re-zeroed below after its last), the results in
     // tp (free between iterations; the loop needs its never-written slots finite, which maxima of finite norms are)
     block_max_rows<18>(m18, h.sx, h.tp, tid);
-#else
-    block_reduce<18>(m18, sall, w.red, tid, TMX_QP_NT);  // ends with every thread holding all values; its barriers free the buffers
-#endif
 #if defined(TMX_FINE) && TMX_FINE == 2
     TMX_TICK(6);
 #endif
@@ -2107,34 +2056,11 @@ TMX_DEVFN int admm_burst_core(const QpWs& w, const DevProblem* P, int n_iter, bo
   return iter_done;
 }
 
-#ifdef TMX_BURST_NOINLINE
-// out-of-line variant: the loop is register-allocated on its own (256 architectural VGPRs); the workspace descriptor
-// is handed over through a small LDS copy
-template <bool RC, int NR, bool INTW>
-__device__ __attribute__((noinline)) static void admm_burst_nl(const QpWs* wsh, const DevProblem* P, int n_iter_in, int keep_last_in,
-                                                              long long* pc_out, long long* tlast_p)
-{
-  const QpWs w = *wsh;
-  long long pc[16] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
-  long long tlast = *tlast_p;
-  admm_burst_core<RC, NR, INTW>(w, P, __builtin_amdgcn_readfirstlane(n_iter_in), __builtin_amdgcn_readfirstlane(keep_last_in) != 0, threadIdx.x, pc, tlast);
-#ifdef TMX_PROFILE
-#pragma unroll
-  for (int q = 0; q < 16; ++q)
-    pc_out[q] += pc[q];
-  *tlast_p = tlast;
-#endif
-}
-#endif
-
-#ifndef TMX_BURST_RC
-#define TMX_BURST_RC 1
-#endif
 TMX_DEVFN int admm_run_fast(const QpWs& w, const DevProblem* P, int n_iter, bool keep_last, int tid, long long* pc, long long& tlast,
                              double* res14 = nullptr, BurstCtl* ctl = nullptr)
 {
   // matrix rows of the dense solve in registers when they fit the fixed register arrays (7-DOF / 30 waypoints: Gs = 22, Zst = 56)
-  const bool rc = TMX_BURST_RC && w.Gs <= 2 * TMX_RC_GP && w.Zst <= 8 * TMX_RC_ZP;
+  const bool rc = w.Gs <= 2 * TMX_RC_GP && w.Zst <= 8 * TMX_RC_ZP;
   // wave roles (all wave-uniform): rows beyond NT sit on the last threads, interior variables on the first NI
   const int wave0 = __builtin_amdgcn_readfirstlane(tid) & ~63;
   const int extra = w.R - TMX_QP_NT;
@@ -2159,17 +2085,8 @@ TMX_DEVFN int admm_run_fast(const QpWs& w, const DevProblem* P, int n_iter, bool
   // (without the upload-time assignment the rows beyond NT are the LAST slots - abs rows in every problem seen so far - and the
   //  two-row waves run the two-slot instantiation unasked, as in rounds 2 - 5)
   const bool aux2 = (two && rperm == nullptr) || __builtin_amdgcn_ballot_w64(my2) != 0ULL;
-#ifdef TMX_BURST_NOINLINE
-  QpWs* wsh = reinterpret_cast<QpWs*>(w.wself);
-  if (tid == 0)
-    *wsh = w;
-  TMX_SYNC();
-#define TMX_BURST_CALL(RCv, NRv, INTv) (admm_burst_nl<RCv, NRv, INTv>(wsh, P, n_iter, keep_last ? 1 : 0, pc, &tlast), n_iter)
-#define TMX_BURST_CALL1(RCv, NRv, INTv) TMX_BURST_CALL(RCv, NRv, INTv)
-#else
 #define TMX_BURST_CALL(RCv, NRv, INTv) admm_burst_core<RCv, NRv, INTv, 2>(w, P, n_iter, keep_last, tid, pc, tlast, res14, ctl)
 #define TMX_BURST_CALL1(RCv, NRv, INTv) admm_burst_core<RCv, NRv, INTv, 1>(w, P, n_iter, keep_last, tid, pc, tlast, res14, ctl)
-#endif
   // (every wave runs the same number of iterations: the epoch-mode decision is made from workgroup-wide reductions)
   int done;
   if (!rc)

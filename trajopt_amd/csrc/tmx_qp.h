@@ -158,10 +158,7 @@ TMX_DEVFN void block_reduce(double (&v)[K], const bool (&is_sum)[K], double* red
 //   part : >= 256 + 16 * (K - 16) doubles of LDS scratch (readable up to 288), fin : >= K doubles; NT = 256; K <= 18
 TMX_DEVFN double raw_max_f64(double a, double b)
 {
-#ifndef TMX_RAW_MAX_ASM
-#define TMX_RAW_MAX_ASM 1
-#endif
-#if TMX_IS_GCN && TMX_RAW_MAX_ASM
+#if TMX_IS_GCN
   double r;
   asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
   return r;
@@ -169,7 +166,7 @@ TMX_DEVFN double raw_max_f64(double a, double b)
   return fmax(a, b);
 #endif
 }
-#if TMX_IS_GCN && !defined(TMX_NO_SCHED_FENCE)
+#if TMX_IS_GCN
 #define TMX_SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
 #else
 #define TMX_SCHED_FENCE() ((void)0)
@@ -1127,10 +1124,8 @@ TMX_DEVFN void kkt_factor(const QpWs& w, const DevProblem* P, int mode, double s
   // row r = list entry q + (l >> 4); B operand: coef_r[l & 15] of the same row; the rows enter in list order, as in the scalar
   // loop below, which problems with rows on two waypoints and the host build keep).  D layout: lane l, register q = entry
   // ((l >> 4) + 4 q, l & 15).
-#ifndef TMX_MFMA_ASSEMBLY
-#define TMX_MFMA_ASSEMBLY 1  // 0: the scalar list-order accumulation everywhere (diagnostic builds: isolates the matrix-core path)
-#endif
-  const bool mfma_blocks = TMX_MFMA_ASSEMBLY && !(P->dbg_flags & 1) && D <= 16 && (NT & 63) == 0 && !TMX_HAS_PAIRS(w);
+  // (DevProblem::dbg_flags bit 0 selects the scalar loop at run time: isolates the matrix-core path)
+  const bool mfma_blocks = !(P->dbg_flags & 1) && D <= 16 && (NT & 63) == 0 && !TMX_HAS_PAIRS(w);
   if (mfma_blocks)
   {
     typedef double tmx_kf_v4d __attribute__((ext_vector_type(4)));

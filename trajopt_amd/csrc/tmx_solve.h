@@ -1098,11 +1098,7 @@ TMX_DEVFN T* tmx_uniform_ptr(T* p)
   return (T*)(((unsigned long long)hi << 32) | lo);
 }
 // The register-resident Ruiz scaling of the dense fast path (tmx_setup.h) as a function of its own, entered once per QP solve: its ~130
-// registers of matrix entries do not join the allocation of the kernel's cold code.  TMX_SETUP_OUTLINED=0 compiles it inline (A/B switch).
-#ifndef TMX_SETUP_OUTLINED
-#define TMX_SETUP_OUTLINED 1
-#endif
-#if TMX_SETUP_OUTLINED
+// registers of matrix entries do not join the allocation of the kernel's cold code.
 __device__ __attribute__((noinline)) static double qp_ruiz_fast_nl(const DevProblem* P_in, const DevBatch* Bt_in, int b_in, unsigned lds_in)
 {
   const DevProblem* P = tmx_uniform_ptr(P_in);
@@ -1120,14 +1116,8 @@ __device__ __attribute__((noinline)) static double qp_ruiz_fast_nl(const DevProb
 #endif
   return ruiz_fast(w, P, P->osqp.scaling, Bt->dims[4 * b], tid);
 }
-#endif
 // The register-resident polish of the dense fast path (tmx_polish.h) as a function of its own, entered once per QP solve: its row and
 // column registers do not join the allocation of the kernel's cold code; in / out through the LDS record (info).
-// TMX_POLISH_OUTLINED=0 compiles it inline (A/B switch).
-#ifndef TMX_POLISH_OUTLINED
-#define TMX_POLISH_OUTLINED 1
-#endif
-#if TMX_POLISH_OUTLINED
 __device__ __attribute__((noinline)) static void qp_polish_fast_nl(const DevProblem* P_in, const DevBatch* Bt_in, int b_in, unsigned lds_in)
 {
   const DevProblem* P = tmx_uniform_ptr(P_in);
@@ -1146,7 +1136,6 @@ __device__ __attribute__((noinline)) static void qp_polish_fast_nl(const DevProb
   TMX_PROF_LEAVE(sh);
   TMX_SYNC();
 }
-#endif
 // between two bursts (iteration `iter` just done): returns 1 when the loop ends
 // (the workgroup's dynamic LDS base travels as a 32-bit LDS offset: no extern __shared__ lookup inside the callees)
 __device__ __attribute__((noinline)) static int qp_check_nl(const DevProblem* P_in, const DevBatch* Bt_in, int b_in, int iter_in, unsigned lds_in)
@@ -1238,14 +1227,8 @@ __device__ __attribute__((noinline)) static void qp_admm_fast_nl(const DevProble
     sh = qp_ws_rebuild(w0, P, Bt, b, smem);
   }
   TMX_PROF_ENTER(sh);
-#ifndef TMX_RES_FROM_REGS
-#define TMX_RES_FROM_REGS 1
-#endif
-#ifndef TMX_BURST_EPOCHS
-#define TMX_BURST_EPOCHS 1  // the burst keeps iterating across residual checks that change nothing (tmx_part.h, BurstCtl)
-#endif
   int iter = 0, ended = 0;
-#if TMX_BURST_EPOCHS && TMX_RES_FROM_REGS
+  // the burst keeps iterating across residual checks that change nothing (tmx_part.h, BurstCtl)
   {
     int done = 0;
     while (true)
@@ -1275,32 +1258,6 @@ __device__ __attribute__((noinline)) static void qp_admm_fast_nl(const DevProble
       }
     }
   }
-#else
-  for (iter = 1; iter <= st.max_iter; ++iter)
-  {
-    int next = st.max_iter;
-    if (st.check_termination)
-      next = min(next, ((iter - 1) / st.check_termination + 1) * st.check_termination);
-    if (st.adaptive_rho && st.adaptive_rho_interval)
-      next = min(next, ((iter - 1) / st.adaptive_rho_interval + 1) * st.adaptive_rho_interval);
-    {
-      QpWs w;
-      sh = qp_ws_rebuild(w, P, Bt, b, smem);
-      admm_run_fast(w, P, next - iter + 1, true, tid, pc, tlast, TMX_RES_FROM_REGS ? sh->res : nullptr);
-      if (TMX_RES_FROM_REGS && tid == 0)
-        sh->have_res = 1;  // ordered before qp_check_nl's reads by the barrier at its entry (qp_ws_rebuild + first block sync)
-      TMX_SYNC();
-    }
-    iter = next;
-    TMX_PROF_LEAVE(sh);
-    ended = qp_check_nl(P, Bt, b, iter, lds_off);
-#ifdef TMX_PROFILE
-    tlast = TMX_CLK();
-#endif
-    if (ended)
-      break;
-  }
-#endif
   if (tid == 0)
   {
     sh->terminated = ended;
@@ -1386,12 +1343,8 @@ TMX_DEVFN void qp_admm_generic_loop(QpWs& w, const DevProblem* P, QpInfo& info, 
 // instantiation keeps the literal band = 0 of qp_ws_carve: no banded code, no calls in the loops of configs 1 - 4.
 // TT = true: the instantiations for TotalTime terms on the block chain (DevProblem::tt_chain; piecewise QP kernels only): every
 // other one keeps the literal ttn = 0 of qp_ws_carve and none of the rank-one correction.
-#ifndef TMX_D10_INSTANTIATION
-#define TMX_D10_INSTANTIATION 1  // block-size-10 instantiation of the pair-row loop for config 3 (10-DOF arm + positioner, HBM workspace): +21.6 %,
-                                 // bit-identical (profiles/r05/r05j_ab_d10_instantiation_cfg3.log).  Rounds 3 - 4 recorded it as "faulted in the
-                                 // 512-thread HBM kernel - memory access fault at address 0, not understood": the stale register of round 5's
-                                 // END_CF finding (trajopt_amd/csrc/Makefile)
-#endif
+// The block-size-10 instantiation of the pair-row loop serves config 3 (10-DOF arm + positioner, HBM workspace): +21.6 %, bit-identical
+// (profiles/r05/r05j_ab_d10_instantiation_cfg3.log).
 template <bool HBM, bool PAIRS, int DC, bool BAND = false, bool TT = false>
 __device__ __attribute__((noinline)) static void qp_admm_generic_nl(const DevProblem* P_in, const DevBatch* Bt_in, int b_in, unsigned lds_in,
                                                                   double* work_in, int chain_in_lds)
@@ -1422,11 +1375,8 @@ __device__ __attribute__((noinline)) static void qp_admm_generic_nl(const DevPro
 #endif
   rows_compact_attach(w);
 #if TMX_LINK_ROWS
-#ifndef TMX_DBG_SWEEP_REGS
-#define TMX_DBG_SWEEP_REGS 1  // (diagnostic builds: 0 = the LDS-exchange walk of the dense-coupling chain everywhere)
-#endif
-  w.sweep_regs = PAIRS && TMX_DBG_SWEEP_REGS;
-  w.sweep_inline = PAIRS && !HBM && TMX_DBG_SWEEP_REGS;
+  w.sweep_regs = PAIRS;
+  w.sweep_inline = PAIRS && !HBM;
 #endif
   if (BAND)  // (banded objectives go with single-joint difference rows only, never with general pair rows: tmx_problem_upload)
     qp_ws_attach_band(w, P->band, Bt->band_ws + (size_t)b * (size_t)Bt->band_stride, (PAIRS && P->band_rows) ? P->n_link : 0);
@@ -1781,7 +1731,7 @@ TMX_DEVFN void qp_solve_block(const DevProblem* P, const DevBatch* Bt, int b, do
 #if TMX_IS_DEVICE
   if (fast_setup)
   {
-#if TMX_ADMM_OUTLINED && TMX_SETUP_OUTLINED
+#if TMX_ADMM_OUTLINED
     unsigned lds_off = (unsigned)(size_t)smem;  // (opaque: see the call of qp_admm_fast_nl below)
     TMX_ASM_OPAQUE_SGPR(lds_off);
     w.c = qp_ruiz_fast_nl(P, Bt, b, lds_off);
@@ -2241,10 +2191,8 @@ TMX_DEVFN void qp_solve_block(const DevProblem* P, const DevBatch* Bt, int b, do
       {
         if (P->D == 7)
           qp_admm_generic_nl<HBM, true, 7>(P, Bt, b, lds_off, HBM ? smem : nullptr, chain_lds != nullptr ? 1 : 0);
-#if TMX_D10_INSTANTIATION
         else if (HBM && P->D == 10)  // config 3 (10-DOF arm + positioner, HBM workspace)
           qp_admm_generic_nl<HBM, true, 10>(P, Bt, b, lds_off, HBM ? smem : nullptr, chain_lds != nullptr ? 1 : 0);
-#endif
         else
           qp_admm_generic_nl<HBM, true, 0>(P, Bt, b, lds_off, HBM ? smem : nullptr, chain_lds != nullptr ? 1 : 0);
       }
@@ -2297,7 +2245,7 @@ TMX_DEVFN void qp_solve_block(const DevProblem* P, const DevBatch* Bt, int b, do
   // generic polish below: same bits
   if (TMX_UNI_B(fast && P->polish_fast != 0 && !(P->dbg_flags & 4) && w.WL == nullptr))
   {
-#if TMX_ADMM_OUTLINED && TMX_POLISH_OUTLINED
+#if TMX_ADMM_OUTLINED
     QpShared* sh = reinterpret_cast<QpShared*>(w.wself);
     if (tid == 0)
       sh->info = info;

@@ -340,11 +340,8 @@ TMX_DEVFN void sqp_update_fast(const DevProblem* P, const DevBatch* Bt, int b, d
 }
 
 // As functions of their own, entered once per convexification / per step (as qp_ruiz_fast_nl / qp_polish_fast_nl): their registers do
-// not join the allocation of the kernel's cold code.  TMX_STEP_OUTLINED=0 compiles them inline (A/B switch).
-#ifndef TMX_STEP_OUTLINED
-#define TMX_STEP_OUTLINED 1
-#endif
-#if TMX_ADMM_OUTLINED && TMX_STEP_OUTLINED
+// not join the allocation of the kernel's cold code.
+#if TMX_ADMM_OUTLINED
 __device__ __attribute__((noinline)) static void qp_structure_fast_nl(const DevProblem* P_in, const DevBatch* Bt_in, int b_in, unsigned lds_in)
 {
   const DevProblem* P = tmx_uniform_ptr(P_in);

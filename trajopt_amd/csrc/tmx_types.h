@@ -250,12 +250,12 @@ struct DevBatch
 };
 
 // rows of a waypoint the register-resident Ruiz scaling keeps per column (tmx_setup.h); the grouped e buffer (QpWs::hr) is padded by
-// as many entries, which is what the burst's own column cache reads (16 + 2 TMX_CJX, tmx_part.h)
+// as many entries, which is what the burst's own column cache reads (16 + 2 CJX of admm_burst_core, tmx_part.h)
 #define TMX_SETUP_COL 18
 // The ADMM loop of the dense fast path as separately compiled device functions (tmx_solve.h: qp_admm_fast_nl /
 // qp_check_nl).  Default on for the device build.
 #ifndef TMX_ADMM_OUTLINED
-#if defined(TMX_BURST_NOINLINE) || defined(TMX_HOST_EMU)
+#ifdef TMX_HOST_EMU
 #define TMX_ADMM_OUTLINED 0
 #else
 #define TMX_ADMM_OUTLINED 1

@@ -42,7 +42,9 @@ names = ["setup", "WALL(10ns)", "ADMM loop | generic: phase A", "check_term | ge
 # As with TMX_FINE=1, the reused slots keep their own phases: subtract the rows of a plain -DTMX_PROFILE run of the same commit.
 if fine5:
     names[11], names[12] = "qp_structure: P hashes + reduction", "eval+update: decision + log + accept copy"
-    names[13], names[14] = "f:assemble + eval+update: exact evaluation", "f:G inverses + eval+update: model values"
+    # (on a problem of DevProblem::eval_fast slot 13 holds the merged pass of tmx_eval.h, exact evaluation and model values, and slot 14
+    #  only its own phase "f:G inverses")
+    names[13], names[14] = "f:assemble + eval+update: exact evaluation (eval_fast: + model values)", "f:G inverses + eval+update: model values"
     names[15], names[6] = "f:Schur+Zs + qp_structure: prefix counts + column pointers", "residuals+rho + qp_structure: hashing walks of A"
 out = list(out)
 # Slot 5 is a phase TIME only on the generic path ("phase C").  On the dense fast path (config 1 without smoothing costs) the

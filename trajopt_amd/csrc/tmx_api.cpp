@@ -1580,6 +1580,25 @@ static Placement place_workspace(const Lowered& L, const EngineChoice& E, const 
                     !(pl.coef_far & 2))
                        ? 1
                        : 0;
+    // the evaluation side of that step (tmx_eval.h): the slot kinds step_eval_fast evaluates, velocity kinds 0 and 1 (what step_fast
+    // leaves: no stencil costs, trajopt_sco), and its tables fit the LDS of the QP workspace, dead at that point of the step; then the
+    // hashes of P for every n = NX .. n_max
+    bool kinds_ok = true;
+    for (int k : L.kind)
+      kinds_ok = kinds_ok && tmx_step_eval_kind(k);
+    for (int k : L.vel_kind)
+      kinds_ok = kinds_ok && (k == 0 || k == 1);
+    const size_t qp_lds = qp_smem_bytes(D, T, R, NA, R2, pl.coef_far);
+    pl.eval_fast = (pl.step_fast && kinds_ok && qp_lds <= 160 * 1024 &&
+                    tmx_step_eval_doubles(R, D * T, (int)L.vel_first.size(), L.n_costs, L.n_cnts) * sizeof(double) <= qp_lds &&
+                    tmx_cvx_fast_doubles((int)L.cp_t.size(), D, D * T) * sizeof(double) <= qp_lds)
+                       ? 1
+                       : 0;
+    if (pl.eval_fast)
+    {
+      pl.p_hash.assign(2 * (size_t)(P.n_max - P.NX + 1), 0ULL);
+      tmx_build_p_hash_table(L.p_colptr.data(), L.pd.data(), L.po.data(), D, P.NX, P.n_max, P.nnzP, pl.p_hash.data());
+    }
   }
   pl.smem_small = small_smem_bytes(L, P);
 #if TMX_IS_DEVICE
@@ -1737,6 +1756,9 @@ static tmx_status upload_tables(tmx_ctx* ctx, const Lowered& L, const Placement&
   P.setup_fast = pl.setup_fast;
   P.polish_fast = pl.polish_fast;
   P.step_fast = pl.step_fast;
+  P.eval_fast = pl.eval_fast;
+  if (pl.eval_fast)
+    UP(p_hash, pl.p_hash);
   P.tt_place = pl.tt_place;
   P.wave_ok = pl.wave_ok;
   P.wv_gmax = pl.wv_gmax;
@@ -3293,7 +3315,8 @@ __attribute__((visibility("default"))) tmx_status tmx_debug_admm_iters(tmx_ctx* 
 
 // debug hook (not in include/tmx.h): diagnostic switches of the uploaded problem (DevProblem::dbg_flags); bit 0 = scalar assembly of the
 // diagonal KKT blocks instead of the MFMA one, bit 1 = generic QP setup, bit 2 = generic polish on the dense fast path, bit 3 = generic
-// SQP shell around the QP solve (qp_structure) on a problem the specialised one can take
+// SQP shell around the QP solve (qp_structure) on a problem the specialised one can take, bit 4 = the hashes of P by the loop over its
+// columns and the generic exact evaluation and model values on a problem of eval_fast
 __attribute__((visibility("default"))) tmx_status tmx_debug_set_flags(tmx_ctx* ctx, int flags)
 {
   if (!ctx || !ctx->have_problem || !ctx->dp)
@@ -3330,6 +3353,15 @@ __attribute__((visibility("default"))) int tmx_debug_step_fast(tmx_ctx* ctx)
   if (!ctx || !ctx->have_problem)
     return -1;
   return ctx->hp.step_fast;
+}
+
+// debug hook (not in include/tmx.h): 1 when the uploaded problem qualifies for the P-hash table and the merged evaluation of the
+// specialised step (DevProblem::eval_fast; the kernels add the launch shape), 0 when not, -1 without a problem
+__attribute__((visibility("default"))) int tmx_debug_eval_fast(tmx_ctx* ctx)
+{
+  if (!ctx || !ctx->have_problem)
+    return -1;
+  return ctx->hp.eval_fast;
 }
 
 // debug hooks (not in include/tmx.h): the engine the upload chose for the QP solves of the uploaded problem, -1 without a problem.

@@ -426,7 +426,22 @@ TMX_DEVFN void sqp_step_block(const DevProblem* P, const DevBatch* Bt, int b, do
   }
   if (Bt->phase[b] == PHASE_CONVEXIFY)
   {
-    convexify_terms(P, x, act, coef, Bt->coef2 + (size_t)b * P->n_link * D, rhs, smem, tid, NT, Bt->rowc + (size_t)b * R, Bt->qdyn + (size_t)b * NX);
+#if TMX_IS_DEVICE
+    // collision and cart-pose rows from shared trig and frame tables (tmx_eval.h) on the problems of eval_fast, under the switch of the
+    // structure pass; DevProblem::dbg_flags bit 4 keeps the generic convexification: same bytes
+    if (TMX_UNI_B(!HBM && NT == TMX_QP_NT && P->step_fast != 0 && P->eval_fast != 0 && !(P->dbg_flags & (8 | 16)) && TMX_FAST_ALLOWED))
+    {
+#if TMX_ADMM_OUTLINED && !(defined(TMX_PROFILE) && defined(TMX_FINE))
+      unsigned lds_off = (unsigned)(size_t)smem;  // (opaque: see the call of qp_admm_fast_nl)
+      TMX_ASM_OPAQUE_SGPR(lds_off);
+      convexify_fast_nl(P, Bt, b, lds_off);
+#else
+      convexify_fast(P, x, act, coef, rhs, smem, tid);
+#endif
+    }
+    else
+#endif
+      convexify_terms(P, x, act, coef, Bt->coef2 + (size_t)b * P->n_link * D, rhs, smem, tid, NT, Bt->rowc + (size_t)b * R, Bt->qdyn + (size_t)b * NX);
 #ifdef TMX_PROFILE
     if (tid == 0)
     {
@@ -472,22 +487,36 @@ TMX_DEVFN void sqp_step_block(const DevProblem* P, const DevBatch* Bt, int b, do
   for (int v = tid; v < NX; v += NT)
     xn[v] = xq[v];
   TMX_SYNC();
-  evaluate_terms(P, xn, Bt->new_cost_vals + (size_t)b * P->n_costs, Bt->new_cnt_viols + (size_t)b * P->n_cnts, smem, tid, NT);
 #if defined(TMX_PROFILE) && defined(TMX_FINE) && TMX_FINE == 5
   [[maybe_unused]] long long* const f5_tl = &tp0;
   [[maybe_unused]] long long* const f5_pc = Bt->prof + (size_t)b * 16;
 #endif
-  TMX_F5_TICK(13);
 #if TMX_IS_DEVICE
-  // the decision fed from LDS and the step log written by the workgroup (tmx_step.h), under the switch of the structure pass
-  if (TMX_UNI_B(!HBM && NT == TMX_QP_NT && P->step_fast != 0 && !(P->dbg_flags & 8) && TMX_FAST_ALLOWED))
+  // the decision fed from LDS and the step log written by the workgroup (tmx_step.h), under the switch of the structure pass; on the
+  // problems of eval_fast the exact evaluation and the model values run with it as one specialised pass (tmx_eval.h) in place of
+  // evaluate_terms - DevProblem::dbg_flags bit 4 keeps the generic evaluation and model values: same bits
+  const bool step_fast = TMX_UNI_B(!HBM && NT == TMX_QP_NT && P->step_fast != 0 && !(P->dbg_flags & 8) && TMX_FAST_ALLOWED);
+  const bool merged = step_fast && TMX_UNI_B(P->eval_fast != 0 && !(P->dbg_flags & 16));
+  if (!merged)
+#endif
+  {
+    evaluate_terms(P, xn, Bt->new_cost_vals + (size_t)b * P->n_costs, Bt->new_cnt_viols + (size_t)b * P->n_cnts, smem, tid, NT);
+    TMX_F5_TICK(13);
+  }
+#if TMX_IS_DEVICE
+  if (step_fast)
   {
 #if TMX_ADMM_OUTLINED && !(defined(TMX_PROFILE) && defined(TMX_FINE))
     unsigned lds_off = (unsigned)(size_t)smem;  // (opaque: see the call of qp_admm_fast_nl)
     TMX_ASM_OPAQUE_SGPR(lds_off);
     sqp_update_fast_nl(P, Bt, b, lds_off);
 #else
-    sqp_update_fast(P, Bt, b, smem, tid TMX_F5_ARGS(&tp0, Bt->prof + (size_t)b * 16));
+    if (merged)
+    {
+      step_eval_fast(P, Bt, b, smem, tid);
+      TMX_F5_TICK(13);  // (exact evaluation and model values; slot 14 stays empty)
+    }
+    sqp_update_fast(P, Bt, b, smem, tid, merged TMX_F5_ARGS(&tp0, Bt->prof + (size_t)b * 16));
 #endif
   }
   else

@@ -17,6 +17,7 @@
 // (tests/test_fast_step.py compares the two in one library).
 #pragma once
 #include "tmx_solve.h"
+#include "tmx_eval.h"
 
 #define TMX_STEP_CP_PASSES 6  // passes of NT columns of the column-pointer scan: NX + 2 R + 1 <= 256 + 1024 + 1
 
@@ -203,49 +204,27 @@ TMX_DEVFN void qp_structure_fast(const DevProblem* P, const int* active, const d
         row_term(mg + col, pos + 1);
       }
   TMX_F5_TICK(6);
-  // P: static pattern over the primary vars (upper triangle): (v-D, v) if po != 0 ; (v, v) if pd != 0; aux columns are empty
-  unsigned long long hP = 0ULL, wsP = 0ULL;
+  // P: static pattern over the primary vars (upper triangle): (v-D, v) if po != 0 ; (v, v) if pd != 0; aux columns are empty.  Its
+  // hashes depend on n alone: the upload-time table (DevProblem::p_hash, tmx_eval.h) on the problems that have one, else - and under
+  // dbg_flags bit 4 - the sum over the columns
+  const bool p_tab = TMX_UNI_B(P->eval_fast != 0 && !(P->dbg_flags & 16));
+  if (!p_tab)
   {
-    const int pp_bytes = n + 1, pp_full = pp_bytes / 8, pp_rem = pp_bytes % 8;
-    const int pi_full = P->nnzP / 8, pi_rem = P->nnzP % 8;
-    auto p_term = [&](long long row, int run) {
-      hP += tmx_hash_term(row, (uint64_t)run, 2);
-      if (run < pi_full)
-        wsP += tmx_hash_term(row, (uint64_t)run, 12);
-      else if (run == pi_full && pi_rem > 0)
-        wsP += tmx_hash_term((long long)((unsigned long long)row & ((1ULL << (8 * pi_rem)) - 1ULL)), (uint64_t)run, 12);
-    };
+    unsigned long long hP = 0ULL, wsP = 0ULL;
     for (int c = tid; c <= n; c += NT)
-    {
-      int run = (c <= NX) ? P->p_colptr[c] : P->nnzP;
-      const long long val = run;
-      hP += tmx_hash_term(val, (uint64_t)c, 1);
-      if (c < pp_full)
-        wsP += tmx_hash_term(val, (uint64_t)c, 11);
-      else if (c == pp_full && pp_rem > 0)
-        wsP += tmx_hash_term((long long)((unsigned long long)val & ((1ULL << (8 * pp_rem)) - 1ULL)), (uint64_t)c, 11);
-      if (c < NX)
-      {
-        if (c >= D && P->po[c - D] != 0.0)
-        {
-          p_term(c - D, run);
-          ++run;
-        }
-        if (P->pd[c] != 0.0)
-          p_term(c, run);
-      }
-    }
+      p_hash_column(P->p_colptr, P->pd, P->po, D, NX, P->nnzP, n, c, hP, wsP);
+    TMX_ATOMIC_ADD_U64(&acc[0], hP);
+    TMX_ATOMIC_ADD_U64(&acc[2], wsP);
   }
-  TMX_ATOMIC_ADD_U64(&acc[0], hP);
   TMX_ATOMIC_ADD_U64(&acc[1], hA);
-  TMX_ATOMIC_ADD_U64(&acc[2], wsP);
   TMX_ATOMIC_ADD_U64(&acc[3], wsA);
   TMX_SYNC();
   if (tid == 0)
   {
-    hashes[0] = acc[0];
+    const unsigned long long* e = P->p_hash + 2 * (size_t)(n - NX);  // (read with p_tab only)
+    hashes[0] = p_tab ? e[0] : acc[0];
     hashes[1] = acc[1];
-    hashes[2] = acc[2];
+    hashes[2] = p_tab ? e[1] : acc[2];
     hashes[3] = acc[3];
   }
   TMX_SYNC();
@@ -258,7 +237,7 @@ TMX_DEVFN void qp_structure_fast(const DevProblem* P, const int* active, const d
 // copies - the sums stay serial, in the reference's order, on the same values (sqp_decide_io) - and the workgroup writes the step log,
 // one entry per thread.  The scalar bookkeeping and the merit inflation stay on thread 0, in their order.
 // Room (DevProblem::step_fast): n_costs + 2 n_cnts + 1 doubles more than the model values need fit the scratch of evaluate_terms.
-TMX_DEVFN void sqp_update_fast(const DevProblem* P, const DevBatch* Bt, int b, double* smem, int tid TMX_F5_PARAMS)
+TMX_DEVFN void sqp_update_fast(const DevProblem* P, const DevBatch* Bt, int b, double* smem, int tid, bool have_model TMX_F5_PARAMS)
 {
   constexpr int NT = TMX_QP_NT;
   const int NX = P->NX, nc = P->n_costs, nv = P->n_cnts;
@@ -276,7 +255,8 @@ TMX_DEVFN void sqp_update_fast(const DevProblem* P, const DevBatch* Bt, int b, d
   const double* new_viol = Bt->new_cnt_viols + (size_t)b * nv;
   const double* merit = Bt->merit + (size_t)b * nv;
   const bool solved = Bt->cvx[b] == TMX_CVX_SOLVED && Bt->phase[b] != PHASE_DONE;
-  if (solved)
+  // (have_model: step_eval_fast, tmx_eval.h, has left the model values with the exact evaluation)
+  if (solved && !have_model)
     sqp_model_values<false>(P, Bt, b, Bt->xq + (size_t)b * P->n_max, smem, tid, NT);  // (ends with a barrier: its scratch is dead)
   TMX_F5_TICK(14);
   for (int k = tid; k < nc; k += NT)
@@ -359,7 +339,22 @@ __device__ __attribute__((noinline)) static void sqp_update_fast_nl(const DevPro
   const int b = __builtin_amdgcn_readfirstlane(b_in);
   const int tid = threadIdx.x;
   double* smem = (double*)(tmx_lds_d*)(size_t)(unsigned)__builtin_amdgcn_readfirstlane((int)lds_in);
-  sqp_update_fast(P, Bt, b, smem, tid);
+  // on the problems of DevProblem::eval_fast the caller has skipped evaluate_terms: exact evaluation and model values as one pass
+  // (tmx_eval.h) in front of the decision
+  const bool merged = TMX_UNI_B(P->eval_fast != 0 && !(P->dbg_flags & 16));
+  if (merged)
+    step_eval_fast(P, Bt, b, smem, tid);
+  sqp_update_fast(P, Bt, b, smem, tid, merged);
+}
+// the convexification of the problems of DevProblem::eval_fast (tmx_eval.h)
+__device__ __attribute__((noinline)) static void convexify_fast_nl(const DevProblem* P_in, const DevBatch* Bt_in, int b_in, unsigned lds_in)
+{
+  const DevProblem* P = tmx_uniform_ptr(P_in);
+  const DevBatch* Bt = tmx_uniform_ptr(Bt_in);
+  const int b = __builtin_amdgcn_readfirstlane(b_in);
+  const int tid = threadIdx.x;
+  double* smem = (double*)(tmx_lds_d*)(size_t)(unsigned)__builtin_amdgcn_readfirstlane((int)lds_in);
+  convexify_fast(P, Bt->x + (size_t)b * P->NX, Bt->active + (size_t)b * P->R, Bt->coef + (size_t)b * P->R * P->D, Bt->rhs + (size_t)b * P->R, smem, tid);
 }
 #endif
 #endif

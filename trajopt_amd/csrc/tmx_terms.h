@@ -49,7 +49,8 @@ TMX_DEVFN void tf_inv(const Tf3& A, Tf3& C)
   for (int r = 0; r < 3; ++r)
     C.t[r] = -(C.R[3 * r + 0] * A.t[0] + C.R[3 * r + 1] * A.t[1] + C.R[3 * r + 2] * A.t[2]);
 }
-TMX_DEVFN void tf_joint_motion(const double* ax, int type, double q, Tf3& T)
+// (s, c) = tmx_sincos(q) of a revolute joint (type 0; unused otherwise): the callers that keep a table of them (tmx_eval.h) enter here
+TMX_DEVFN void tf_joint_motion_sc(const double* ax, int type, double q, double s, double c, Tf3& T)
 {
   for (int k = 0; k < 9; ++k)
     T.R[k] = 0.0;
@@ -57,8 +58,6 @@ TMX_DEVFN void tf_joint_motion(const double* ax, int type, double q, Tf3& T)
   T.t[0] = T.t[1] = T.t[2] = 0.0;
   if (type == 0)
   {
-    double c, s;
-    tmx_sincos(q, &s, &c);
     const double v = 1.0 - c;
     const double x = ax[0], y = ax[1], z = ax[2];
     T.R[0] = c + x * x * v;
@@ -77,6 +76,13 @@ TMX_DEVFN void tf_joint_motion(const double* ax, int type, double q, Tf3& T)
     T.t[1] = ax[1] * q;
     T.t[2] = ax[2] * q;
   }
+}
+TMX_DEVFN void tf_joint_motion(const double* ax, int type, double q, Tf3& T)
+{
+  double c = 1.0, s = 0.0;
+  if (type == 0)
+    tmx_sincos(q, &s, &c);
+  tf_joint_motion_sc(ax, type, q, s, c, T);
 }
 
 // world transform of link `upto` (child of joint `upto`).  The joint values come from a callable (joint index -> value)
@@ -301,12 +307,10 @@ __device__ __attribute__((noinline)) static int hull_closest_nl(const double* hv
 
 // sphere-vs-sphere signed distance for contact slot (link sphere s, obstacle o) at joint values q
 // HULL: the instantiation carries the convex-hull link code (piecewise kernels of ST problems only)
+// (contact_distance_at: the same with the world frame L of the sphere's link as an input)
 template <bool HULL = false>
-TMX_DEVFN double contact_distance(const DevProblem* P, const double* q, int s, int o, double n[3], double pw[3])
+TMX_DEVFN double contact_distance_at(const DevProblem* P, const Tf3& L, int s, int o, double n[3], double pw[3])
 {
-  Tf3 L;
-  const int link = P->ls_link[s];
-  fk_link(P, q, link, L);
   if constexpr (HULL)
     if (P->n_ls_hull > 0 && P->ls_hull[2 * s + 1] > 0)
     {
@@ -350,6 +354,14 @@ TMX_DEVFN double contact_distance(const DevProblem* P, const double* q, int s, i
   for (int r = 0; r < 3; ++r)
     pw[r] = c[r] + rs * n[r];
   return len - rs - P->ob_radius[o];
+}
+template <bool HULL = false>
+TMX_DEVFN double contact_distance(const DevProblem* P, const double* q, int s, int o, double n[3], double pw[3])
+{
+  Tf3 L;
+  const int link = P->ls_link[s];
+  fk_link(P, q, link, L);
+  return contact_distance_at<HULL>(P, L, s, o, n, pw);
 }
 
 // ---- LVS_DISCRETE / (LVS_)CONTINUOUS collision on a segment (q0 = x[t], q1 = x[t+1]) --------------------------------

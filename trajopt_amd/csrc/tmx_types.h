@@ -154,7 +154,9 @@ struct DevProblem
   // the scalar list-order loop instead of v_mfma_f64_16x16x4_f64 (tests/test_gpu_parity.py compares the two on the same QP);
   // bit 1 = the generic load and Ruiz scaling of the QP setup on a problem of the dense fast path (setup_fast below);
   // bit 2 = the generic polish on such a problem (polish_fast below);
-  // bit 3 = the generic SQP shell around the QP solve (qp_structure) on a problem the specialised one can take (step_fast below)
+  // bit 3 = the generic SQP shell around the QP solve (qp_structure) on a problem the specialised one can take (step_fast below);
+  // bit 4 = the hashes of P by the loop over its columns and the generic exact evaluation and model values (evaluate_terms,
+  //         sqp_model_values) on a problem that qualifies for the table and the merged evaluation (eval_fast below)
   int dbg_flags;
   // TotalTime terms ON THE BLOCK CHAIN (tmx_problem_upload: the only reason for the dense engine are these terms and the QP is over
   // its size limit, or TMX_TOTAL_TIME_CHAIN=1): tt_chain = n_tt (<= TMX_TT_MAX) and qp_dense = 0 - the structured QP kernels carry
@@ -183,6 +185,13 @@ struct DevProblem
   // trajopt_sco flavour.  dbg_flags bit 3 selects the generic code on such a problem (same bits; tests/test_fast_step.py compares the
   // two in one library).
   int step_fast;
+  // eval_fast: the evaluation side of the specialised step (tmx_eval.h: step_eval_fast) can take the problem - the conditions of
+  // step_fast, only fixed, cart-pose, joint-pos and collision slots, velocity terms of kinds 0 and 1, and its trig and frame tables
+  // fit the LDS of the QP workspace (tmx_step_eval_doubles, tmx_cvx_fast_doubles).  p_hash: (hashP, wsP) of the static objective pattern for every number of QP variables n = NX .. n_max,
+  // two u64 per entry, built at upload (tmx_build_p_hash_table; null without eval_fast).  dbg_flags bit 4 selects the generic code on
+  // such a problem (same bits; tests/test_fast_eval.py compares the two in one library).
+  unsigned long long* p_hash;
+  int eval_fast;
 };
 TMX_HOSTDEVFN int slot_is_diff(int kind) { return kind == SLOT_JOINTVEL || kind == SLOT_JOINTVEL_INEQ; }
 #define TMX_TV_REC 5  // DevBatch::tv_aff record of one segment: cleaned Jacobian entries on x[t][j], x[t+1][j], tau[t+1] (upper row), constants of the upper / lower row

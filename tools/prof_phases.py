@@ -1,14 +1,18 @@
 """Phase profile (needs a -DTMX_PROFILE build: make -C trajopt_amd/csrc EXTRA=-DTMX_PROFILE).
    python tools/prof_phases.py [B] [full|first] [lib.so] [config[s]]   - first QP solve only (default) or the whole optimize() run
-   ("full"); config 1 (default), 2, 3 or 4; the word "fine5" anywhere among the arguments names the slots of a -DTMX_PROFILE -DTMX_FINE=5 build"""
+   ("full"); config 1 (default), 2, 3 or 4, or a problem of tests/test_band_pair_chain.py ("H", "H-nocost": without its smoothing
+   costs); the word "fine5" anywhere among the arguments names the slots of a -DTMX_PROFILE -DTMX_FINE=5 build"""
 import sys, os, ctypes as C, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from trajopt_amd import configs, abi, runtime
 fine5 = "fine5" in sys.argv[1:]  # (a word, not a position: taken out before the positional arguments are read)
 sys.argv = [a for a in sys.argv if a != "fine5"]
-smooth = len(sys.argv) > 4 and sys.argv[4].endswith("s")  # "1s": config 1 + acceleration and jerk smoothing costs (banded path)
-cid = int(sys.argv[4].rstrip("s")) if len(sys.argv) > 4 else 1
+# a problem of tests/test_band_pair_chain.py in place of the configuration: "H", "F", ... (squared acceleration / jerk costs next to
+# pair rows); "H-nocost" drops the smoothing costs (the same rows on the segmented dense-coupling chain)
+bp_name = sys.argv[4] if len(sys.argv) > 4 and not sys.argv[4][0].isdigit() else None
+smooth = bp_name is None and len(sys.argv) > 4 and sys.argv[4].endswith("s")  # "1s": config 1 + acceleration and jerk smoothing costs (banded path)
+cid = int(sys.argv[4].rstrip("s")) if len(sys.argv) > 4 and bp_name is None else 1
 pci, s, g = {1: configs.config1, 2: configs.config2, 3: configs.config3, 4: configs.config4}[cid]()
 if smooth:
     from trajopt_amd.problem import JointAccTermInfo, JointJerkTermInfo
@@ -19,6 +23,18 @@ desc = pci.to_desc()
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 256
 full = len(sys.argv) > 2 and sys.argv[2] == "full"
 x0 = configs.seeds_for(cid, pci, s, g, B, **({"sigma": 0.05} if cid in (3, 4) else {}))
+if bp_name is not None:
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import test_band_pair_chain as bp
+    from trajopt_amd.problem import JointAccTermInfo, JointJerkTermInfo
+    for k in (bp.SWITCH, "TMX_DENSE_QP_MAX_N"):
+        os.environ.pop(k, None)
+    pci, x0 = bp.ALL[bp_name.split("-")[0]](B)
+    if bp_name.endswith("-nocost"):
+        pci.cost_infos = [ti for ti in pci.cost_infos if not isinstance(ti, (JointAccTermInfo, JointJerkTermInfo))]
+    desc = pci.to_desc()
+    cid = 0
+    print("problem", bp_name, "of tests/test_band_pair_chain.py")
 ctx = runtime.Context(0, sys.argv[3] if len(sys.argv) > 3 else None)
 ctx.upload(desc, abi.default_sqp_params(), configs.osqp_settings_config4() if cid == 4 else abi.default_osqp_settings())
 ctx.set_x0(x0)

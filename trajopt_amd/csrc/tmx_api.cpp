@@ -1469,12 +1469,39 @@ static EngineChoice choose_engine(const Lowered& L, const DevProblem& P, const U
     else
       qp_dense = true;
   }
-  // squared acceleration / jerk costs alone keep the structured solver (banded block factorisation of the generic path); together
-  // with general pair rows (the dense-coupling chain has no banded variant) or function costs: dense engine
+  // squared acceleration / jerk costs alone keep the structured solver (banded block factorisation of the generic path).  Together
+  // with general pair rows (LVS / cast collision rows, CartVel rows: dense coupling blocks) small problems keep the dense engine, bit
+  // for bit as before; a problem over that engine's size limit whose ONLY reason for it is this combination runs on the banded
+  // factorisation with a dense first coupling block (DevProblem::band_pairs: K_{t+1,t} = Cd_t', the far couplings stay diagonal),
+  // on the piecewise driver, whose QP kernels hold the pair-row + banded ADMM loop.  TMX_BAND_PAIR_CHAIN: "1" that route at any size,
+  // "0" never (the dense engine and its limit).  Next to acceleration / jerk ROWS with general pair rows, to time-parameterised terms,
+  // to function costs or in the trajopt_sqp flavour the dense engine stays.
+  std::string bp_why;  // what keeps the combination on the dense engine
   if (band && !E.band_rows && (qp_dense || R2 > 0))
   {
-    qp_dense = true;
-    band = 0;
+    const bool able = TMX_LINK_ROWS && !qp_dense && !L.stencil_rows && R2 > 0 && !L.tt_terms && !L.tv_terms && !L.dyn_p && P.flavor == TMX_FLAVOR_SCO;
+    const bool want = hooks.band_pair_chain == '1' || (hooks.band_pair_chain != '0' && P.n_max > hooks.dense_qp_max_n);
+    E.band_pairs = able && want;
+    if (L.dyn_p)
+      bp_why = "function costs";
+    else if (L.stencil_rows)
+      bp_why = "acceleration / jerk rows";
+    else if (L.tt_terms || L.tv_terms)
+      bp_why = "time-parameterised terms";
+    else if (P.flavor != TMX_FLAVOR_SCO)
+      bp_why = "rows on two waypoints in the trajopt_sqp flavour";
+    else if (qp_dense || !TMX_LINK_ROWS)
+      bp_why = "rows on two waypoints in a build without them";
+    else
+      bp_why = "rows on two waypoints with TMX_BAND_PAIR_CHAIN=0";
+    if (E.band_pairs)
+      st_terms = true;  // (piecewise driver: its QP kernels carry the ROWSK + BANDK instantiations.  The lowering sets L.st_terms for these
+                        //  costs in the trajopt_sqp flavour only; a trajopt_sco problem with squared costs alone runs on k_sqp_pool_band)
+    else
+    {
+      qp_dense = true;
+      band = 0;
+    }
   }
   E.qp_dense = qp_dense;
   E.band = band;
@@ -1498,8 +1525,10 @@ static EngineChoice choose_engine(const Lowered& L, const DevProblem& P, const U
       reason("TotalTime terms next to acceleration / jerk costs or function costs");
     else if (L.tt_terms && L.tv_owner.empty() && !L.stencil_rows)
       reason("TotalTime terms with TMX_TOTAL_TIME_CHAIN=0 (or a build without rows on two waypoints)");
+    // ("... next to rows on two waypoints or function costs": the wording of before for the cases of before; what the route of
+    //  DevProblem::band_pairs leaves is named behind it)
     if (why.empty())
-      reason("acceleration / jerk costs next to rows on two waypoints or function costs");
+      reason("acceleration / jerk costs next to rows on two waypoints or function costs" + (bp_why.empty() ? std::string() : " (here: " + bp_why + ")"));
   }
   return E;
 }
@@ -1948,6 +1977,7 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
   P.st = E.st ? 1 : 0;
   P.tt_chain = E.tt_chain ? (int)L.tt_owner.size() : 0;
   P.tv_chain = E.tv_chain ? 1 : 0;
+  P.band_pairs = E.band_pairs ? 1 : 0;
   P.n_link = E.R2;
   const Placement pl = place_workspace(L, E, P, hooks);
   if ((rc = upload_tables(ctx, L, pl, P)) != TMX_OK)
@@ -3393,6 +3423,14 @@ __attribute__((visibility("default"))) int tmx_debug_tv_chain(tmx_ctx* ctx)
   if (!ctx || !ctx->have_problem)
     return -1;
   return ctx->hp.tv_chain;
+}
+
+// ... and band_pairs (squared acceleration / jerk costs next to general pair rows on the banded factorisation with a dense first coupling)
+__attribute__((visibility("default"))) int tmx_debug_band_pairs(tmx_ctx* ctx)
+{
+  if (!ctx || !ctx->have_problem)
+    return -1;
+  return ctx->hp.band_pairs;
 }
 
 // debug hook (not in include/tmx.h): 1 = fused persistent optimize() kernel (default), 0 = one launch chain per step

@@ -349,6 +349,11 @@ struct QpWs
   int n_link;      // R2
   bool sweep_regs; // the dense-coupling chain sweeps keep their running vector in registers (set by qp_admm_generic_nl<., true> only)
   bool sweep_inline; // ... and are inlined into the loop (LDS-resident kernels)
+  // BANDED OBJECTIVE NEXT TO GENERAL PAIR ROWS (DevProblem::band_pairs): the reduced KKT matrix is block banded with the DENSE first
+  // coupling Cd and the diagonal far couplings po2 / po3; band_factor starts M_1[t] from Cd_t', everything behind the factorisation
+  // (band_solve) reads W only.  The literal false of qp_ws_carve everywhere but in the piecewise QP kernels (qp_ws_attach_band); in
+  // the padding behind sweep_inline: the descriptor has the size it had.
+  bool band_cd;
 #endif
 };
 
@@ -869,6 +874,7 @@ TMX_DEVFN void qp_ws_carve(QpWs& w, double* lds, double* glb, double* far, int D
   w.n_link = R2;
   w.sweep_regs = false;
   w.sweep_inline = false;
+  w.band_cd = false;
   if (R2 > 0)
   {
     if (!cf)
@@ -1441,7 +1447,8 @@ TMX_DEVFN int pspk_segments(const QpWs& w, int NT)
   // (problems with joint - time entries of the objective, QpWs::tvo, walk the chain in ONE piece on every build: the spike-corrected
   //  segments add their products in another order than the plain walk, and the number of segments follows the number of threads -
   //  these problems keep sums whose order does not depend on it, so that host build, SIMT emulation and device give the same bits)
-  if (w.tvo != 0)
+  // (a banded objective next to pair rows, QpWs::band_cd: no dense-coupling chain at all - band_solve walks the factors W)
+  if (w.tvo != 0 || w.band_cd)
     return 0;
   const int P = (NT >> 6) < 4 ? (NT >> 6) : 4;
   return (w.WL != nullptr && TMX_HAS_PAIRS(w) && P >= 2 && w.T >= 2 * P + 2 && P * w.D <= 64) ? P : 0;
@@ -1531,7 +1538,15 @@ TMX_DEVFN double band_col_norm(const QpWs& w, int v)
   return cn;
 }
 // banded problems: the far couplings and the block factors live in their own per-problem HBM slice (DevBatch::band_ws)
-TMX_DEVFN void qp_ws_attach_band(QpWs& w, int band, double* slice, int band_rows = 0)
+// band_pairs: the banded objective sits next to general pair rows (DevProblem::band_pairs) - the first coupling is the dense Cd.
+// Such a workspace has no fast-path region (G is null with pair rows) but the arrays of the dense-coupling chain it does not walk:
+// Cd | Mf | Nb | yb, consecutive in qp_ws_carve (T D^2 each, then NX).  The factors W (band x T D^2 doubles) take that place and the
+// vector between the sweeps that of yb - in LDS when the workspace is: W_1 over Cd, W_2 over Mf, W_3 over Nb.  W_1[t] lands exactly
+// on Cd_t, which band_factor has consumed by then: step t reads Cd_t into M_1[t] (band slice), passes a barrier and only then writes
+// W_1[t]; later steps read Cd_s, s > t, and nothing behind the factorisation reads Cd (kkt_factor rebuilds all of it before the next
+// one).  An HBM workspace keeps Cd in HBM and has Mf | Nb | yb among its chain arrays in LDS (qp_ws_chain_to_lds): the factors of a
+// band-2 problem go there; those of a band-3 problem (3 T D^2) stay in the band slice in HBM.
+TMX_DEVFN void qp_ws_attach_band(QpWs& w, int band, double* slice, int band_rows = 0, bool band_pairs = false)
 {
   w.band = band;
   if (band == 0)
@@ -1554,6 +1569,18 @@ TMX_DEVFN void qp_ws_attach_band(QpWs& w, int band, double* slice, int band_rows
   // that the sweeps of band_solve do not wait for HBM at every block
   if (w.G != nullptr && w.Zs != nullptr && (size_t)(w.Zs - w.G) >= 3 * TDD)
     w.Wb = w.G;
+#if TMX_LINK_ROWS
+  if (band_pairs && w.n_link > 0)
+  {
+    w.band_cd = true;
+    if (w.Mf == w.Cd + TDD && w.Nb == w.Mf + TDD && w.yb == w.Nb + TDD)
+      w.Wb = w.Cd;
+    else if (band == 2 && w.Nb >= w.Mf + TDD && w.yb >= w.Nb + TDD)
+      w.Wb = w.Mf;
+  }
+#else
+  (void)band_pairs;
+#endif
 }
 TMX_HOSTDEVFN size_t qp_band_doubles(int D, int T, int band_rows = 0)
 {
@@ -1614,13 +1641,23 @@ TMX_DEVFN BandWs band_ws_of(const QpWs& w)
   b.band = w.band;
   const size_t TDD3 = 3 * (size_t)w.T * w.D * w.D;
   b.y = (w.Wb != nullptr && w.Wb == w.G && (size_t)(w.Zs - w.G) >= TDD3 + (size_t)w.NX) ? w.G + TDD3 : w.Mb;
+#if TMX_LINK_ROWS
+  if (w.band_cd && (w.Wb == w.Mf || w.Wb == w.Cd))  // (the factors in the place of [Cd |] Mf | Nb: the vector between the sweeps in that of yb, qp_ws_attach_band)
+    b.y = w.yb;
+#endif
   return b;
 }
 TMX_DEVFN double band_coupling(const BandWs& w, int k, int t, int i)
 {
   return k == 1 ? w.po[t * w.D + i] : (k == 2 ? w.po2[t * w.D + i] : w.po3[t * w.D + i]);
 }
-TMX_DEVFN void band_factor_impl(const BandWs& w, int tid, int NT)
+// CD (QpWs::band_cd, a banded objective next to general pair rows): the first coupling K_{t+1,t} is DENSE - the transpose of block
+// (t, t + 1) of the reduced KKT matrix, Cd[t D D + i D + j] with i on waypoint t and j on t + 1 (kkt_factor: diag(po_t) + the pair
+// rows' w_r coef_r c2_r'), (T - 1) D D doubles.  M_1[t] starts from it; po2 / po3 stay the start values of M_2 / M_3; the recurrences,
+// the inversion and band_solve (which reads W only) are the same.  An instantiation of its own, called by the piecewise QP kernels
+// only: the routine of the diagonal couplings - and with it every other kernel - is what it was.
+template <bool CD = false>
+TMX_DEVFN void band_factor_impl(const BandWs& w, int tid, int NT, [[maybe_unused]] const double* Cd = nullptr)
 {
   const int D = w.D, DD = D * D, DS = w.DS, DDS = w.DDS, T = w.T, nb = w.band;
   for (int t = 0; t < T; ++t)
@@ -1676,7 +1713,8 @@ TMX_DEVFN void band_factor_impl(const BandWs& w, int tid, int NT)
         for (int e = tid; e < DD; e += NT)
         {
           const int i = e / D, c = e % D;
-          double val = (i == c) ? band_coupling(w, jj, t, i) : 0.0;
+          // K_{t+jj,t}: diagonal, or - CD, jj = 1 - the transpose of the dense block (t, t + 1)
+          double val = (CD && jj == 1) ? Cd[(size_t)t * DD + c * D + i] : ((i == c) ? band_coupling(w, jj, t, i) : 0.0);
           for (int k = 1; jj + k <= nb && k <= t; ++k)
           {
             const double* A = w.Mb + ((size_t)(jj + k - 1) * T + (t - k)) * DD;
@@ -1974,6 +2012,7 @@ TMX_DEVFN void band_solve_dd_impl(const BandWs& w, double* ddbase, int tid, int 
 
 #if TMX_IS_DEVICE
 __device__ __attribute__((noinline)) static void band_factor_nl(BandWs b) { band_factor_impl(b, threadIdx.x, blockDim.x); }
+__device__ __attribute__((noinline)) static void band_factor_cd_nl(BandWs b, const double* Cd) { band_factor_impl<true>(b, threadIdx.x, blockDim.x, Cd); }
 // band_solve with the two sweeps walked by ONE wave (lane i = component i of the running vectors, which stay in registers; the other
 // components by v_readlane; no barrier per block) - the treatment of the dense-coupling chain (chain_wave_sweep).  Same products,
 // same order of additions as band_solve_impl: bit-identical.  The factors W should sit in LDS (qp_ws_attach_band) - from the HBM
@@ -2131,6 +2170,11 @@ __device__ __attribute__((noinline)) static void band_factor_dd_nl(BandWs b, dou
 __device__ __attribute__((noinline)) static void band_solve_dd_nl(BandWs b, double* ddbase) { band_solve_dd_impl(b, ddbase, threadIdx.x, blockDim.x); }
 TMX_DEVFN void band_factor(const QpWs& w, int, int)
 {
+#if TMX_LINK_ROWS
+  if (w.band_cd)  // (never with polish_dd: that is the polish of problems with difference rows)
+    band_factor_cd_nl(band_ws_of(w), w.Cd);
+  else
+#endif
   if (w.polish_dd)
     band_factor_dd_nl(band_ws_of(w), ws_dd(w));
   else
@@ -2146,6 +2190,11 @@ TMX_DEVFN void band_solve(const QpWs& w, int, int)
 #else
 TMX_DEVFN void band_factor(const QpWs& w, int tid, int NT)
 {
+#if TMX_LINK_ROWS
+  if (w.band_cd)
+    band_factor_impl<true>(band_ws_of(w), tid, NT, w.Cd);
+  else
+#endif
   if (w.polish_dd)
     band_factor_dd_impl(band_ws_of(w), ws_dd(w), tid, NT);
   else

@@ -1378,8 +1378,8 @@ __device__ __attribute__((noinline)) static void qp_admm_generic_nl(const DevPro
   w.sweep_regs = PAIRS;
   w.sweep_inline = PAIRS && !HBM;
 #endif
-  if (BAND)  // (banded objectives go with single-joint difference rows only, never with general pair rows: tmx_problem_upload)
-    qp_ws_attach_band(w, P->band, Bt->band_ws + (size_t)b * (size_t)Bt->band_stride, (PAIRS && P->band_rows) ? P->n_link : 0);
+  if (BAND)  // (banded objectives go with single-joint difference rows, or - DevProblem::band_pairs - with general pair rows: tmx_problem_upload)
+    qp_ws_attach_band(w, P->band, Bt->band_ws + (size_t)b * (size_t)Bt->band_stride, (PAIRS && P->band_rows) ? P->n_link : 0, PAIRS && P->band_pairs != 0);
   QpShared* sh = reinterpret_cast<QpShared*>(w.wself);
   w.rho = sh->rho;
   w.sigma = sh->sigma;
@@ -1434,7 +1434,7 @@ TMX_DEVFN void qp_solve_block(const DevProblem* P, const DevBatch* Bt, int b, do
       qp_ws_chain_to_lds(w, chain_lds);
   }
   if constexpr (BANDK)
-    qp_ws_attach_band(w, P->band, Bt->band_ws + (size_t)b * (size_t)Bt->band_stride, (ROWSK && P->band_rows) ? P->n_link : 0);
+    qp_ws_attach_band(w, P->band, Bt->band_ws + (size_t)b * (size_t)Bt->band_stride, (ROWSK && P->band_rows) ? P->n_link : 0, ROWSK && P->band_pairs != 0);
   // function costs on the structured solver (round 5; piecewise kernels only): the dynamic D x D objective blocks of the waypoints
   // live behind the far region of the per-problem scratch
   [[maybe_unused]] const double* dyn_H = nullptr;
@@ -2185,7 +2185,7 @@ TMX_DEVFN void qp_solve_block(const DevProblem* P, const DevBatch* Bt, int b, do
         else
           qp_admm_generic_nl<HBM, false, 0, false, true>(P, Bt, b, lds_off, HBM ? smem : nullptr, chain_lds != nullptr ? 1 : 0);
       }
-      else if (ROWSK && BANDK && P->band && P->n_link > 0)  // banded path with difference rows of order 2 / 3 (DevProblem::band_rows)
+      else if (ROWSK && BANDK && P->band && P->n_link > 0)  // banded path with difference rows of order 2 / 3 (DevProblem::band_rows) or next to general pair rows (band_pairs)
         qp_admm_generic_nl<HBM, true, 0, true>(P, Bt, b, lds_off, HBM ? smem : nullptr, chain_lds != nullptr ? 1 : 0);
       else if (P->n_link > 0)
       {

@@ -192,6 +192,11 @@ struct DevProblem
   // such a problem (same bits; tests/test_fast_eval.py compares the two in one library).
   unsigned long long* p_hash;
   int eval_fast;
+  // Squared acceleration / jerk costs NEXT TO GENERAL PAIR ROWS (LVS / cast collision, CartVel: dense coupling blocks) over the dense
+  // engine's size limit, or with TMX_BAND_PAIR_CHAIN=1 (tmx_problem_upload): band_pairs = 1, band = 2 | 3 kept and qp_dense = 0 - the
+  // piecewise QP kernels factor the block-banded reduced KKT matrix with a DENSE first coupling (QpWs::Cd, rebuilt by kkt_factor) and
+  // the diagonal far couplings po2 / po3 (band_factor, tmx_qp.h).  0 everywhere else.  (Last, in the padding behind eval_fast.)
+  int band_pairs;
 };
 TMX_HOSTDEVFN int slot_is_diff(int kind) { return kind == SLOT_JOINTVEL || kind == SLOT_JOINTVEL_INEQ; }
 #define TMX_TV_REC 5  // DevBatch::tv_aff record of one segment: cleaned Jacobian entries on x[t][j], x[t+1][j], tau[t+1] (upper row), constants of the upper / lower row

@@ -46,10 +46,11 @@ struct Lowered
   int band = 0;           // acceleration (2) / jerk (3) squared costs: banded objective
 };
 
-// The QP engine of the problem (choose_engine): DevProblem::qp_dense / tt_chain / tv_chain / band_rows / st / band / n_link.
+// The QP engine of the problem (choose_engine): DevProblem::qp_dense / tt_chain / tv_chain / band_rows / band_pairs / st / band / n_link.
 struct EngineChoice
 {
   bool qp_dense = false, tt_chain = false, tv_chain = false, band_rows = false, st = false;
+  bool band_pairs = false;  // squared acceleration / jerk costs next to general pair rows on the banded factorisation with a dense first coupling
   int band = 0;
   int R2 = 0;  // Lowered::R2, or 1 for squared velocity-with-time costs on the chain without a pair row (an unused second-block slot)
   std::string dense_reasons;  // what put the problem on the dense engine, comma-joined (text of the refusal above its size limit)
@@ -59,7 +60,7 @@ struct EngineChoice
 struct UploadHooks
 {
   // first character of the variable ('\0': unset)
-  char total_time_chain, vel_time_chain, force_coef_far, force_compact, row_perm, wave, tt_place;
+  char total_time_chain, vel_time_chain, band_pair_chain, force_coef_far, force_compact, row_perm, wave, tt_place;
   int dense_qp_max_n;  // size limit of the dense QP engine (QP variables incl. penalty variables); TMX_DENSE_QP_MAX_N lifts it for callers who accept the time
   bool verbose;
   static UploadHooks read()
@@ -71,6 +72,7 @@ struct UploadHooks
     UploadHooks h;
     h.total_time_chain = first("TMX_TOTAL_TIME_CHAIN");
     h.vel_time_chain = first("TMX_VEL_TIME_CHAIN");
+    h.band_pair_chain = first("TMX_BAND_PAIR_CHAIN");
     h.force_coef_far = first("TMX_FORCE_COEF_FAR");
     h.force_compact = first("TMX_FORCE_COMPACT");
     h.row_perm = first("TMX_ROW_PERM");

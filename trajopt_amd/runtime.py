@@ -203,6 +203,17 @@ class Context:
         self._chk(self.lib.tmx_workspace_info(self.h, C.byref(a), C.byref(b), C.byref(c)))
         return dict(in_hbm=bool(a.value), lds_bytes=b.value, hbm_bytes_per_problem=c.value)
 
+    def debug_flag(self, name: str) -> int:
+        """a verdict of the upload (debug hooks outside include/tmx.h, declared in abi.DEBUG_HOOKS): -1 without a problem"""
+        fn = getattr(self.lib, "tmx_debug_" + name)
+        fn.argtypes, fn.restype = abi.DEBUG_HOOKS[name]
+        return int(fn(self.h))
+
+    def band_pairs(self) -> bool:
+        """squared acceleration / jerk costs next to rows on two waypoints with dense coupling blocks run on the banded factorisation
+        with a dense first coupling (DevProblem::band_pairs, tmx_debug_band_pairs)"""
+        return self.debug_flag("band_pairs") == 1
+
     def workspace_in_hbm(self) -> bool:
         return self.workspace_info()["in_hbm"]
 

@@ -587,6 +587,33 @@ TMX_API tmx_status tmx_attach_nccl(tmx_ctx* ctx, void* nccl_comm /* ncclComm_t *
  * owner rank (the rank whose shard holds the winning global index), otherwise a copy.  *owner_rank (optional) = that rank.
  * TMX_ERR_STATE when no seed converged anywhere.  Collective: every rank of the communicator must call it.              */
 TMX_API tmx_status tmx_best_trajectory(tmx_ctx* ctx, double* x_out, int32_t* owner_rank);
+/* ---- Multi-query batches: a batch of Q queries x S seeds (problem b belongs to query b / S).  All queries share the uploaded
+ *      description (robot, scene, term list, coefficients, tolerances, engine, placement); each has its own goal targets for
+ *      the terms tmx_query_set_targets accepts.  After tmx_problem_upload a context has one query (the description's own
+ *      targets).  Order of calls: tmx_problem_upload, tmx_queries_set, tmx_query_set_targets (per term), tmx_batch_set_x0*,
+ *      run / launch, tmx_argmin_queries, tmx_best_trajectories.  Targets are set BEFORE tmx_batch_set_x0*: it runs the first
+ *      exact evaluation.  tmx_queries_set and tmx_query_set_targets invalidate the current batch: until the next
+ *      tmx_batch_set_x0* the run, launch, evaluate, convexify and result calls return TMX_ERR_STATE, as they do without an x0. */
+/* The number of queries of the following batches.  n_queries >= 2 allocates the per-query tables and fills every query from the
+ * description's own targets; n_queries == 1 frees them (the one-query path of the kernels).  With n_queries >= 2
+ * tmx_batch_set_x0* return TMX_ERR_INVALID unless batch % n_queries == 0.  TMX_ERR_STATE without an uploaded problem or while a
+ * launch is pending; TMX_ERR_UNSUPPORTED for n_queries >= 2 on a TMX_FLAVOR_SQP problem.  A new tmx_problem_upload returns the
+ * context to one query.                                                                                                       */
+TMX_API tmx_status tmx_queries_set(tmx_ctx* ctx, int32_t n_queries);
+/* The goal targets of term `term` (index into tmx_problem_desc::terms) for every query: targets[n_queries][len].
+ *   TMX_TERM_CART_POSE lowered into cart-pose instances: len = 12, layout of tmx_term::target_pose; applies to every step of the term.
+ *   TMX_TERM_JOINT_POS_EQ_CNT / _INEQ_CNT / _INEQ_COST: len = n_dof, as tmx_term::targets.
+ * TMX_ERR_UNSUPPORTED (reason in tmx_last_error) for every other kind: a CART_POSE term with tolerances is a function term whose
+ * target is a constant of its program; TMX_TERM_JOINT_POS_EQ_COST of the trajopt_sco flavour is baked into the static objective.
+ * TMX_ERR_INVALID for a bad index, a wrong len or non-finite values; TMX_ERR_STATE with one query or while a launch is pending.   */
+TMX_API tmx_status tmx_query_set_targets(tmx_ctx* ctx, int32_t term, const double* targets /* n_queries x len */, int32_t len);
+/* K7 per query: best_index[q] = index IN THE BATCH of the seed of query q with the lowest total_cost among its OPT_CONVERGED seeds
+ * (ties: the lowest index), best_cost[q] its cost; -1 and 1e300 when none converged.  One query: the local tmx_argmin.  LOCAL TO THE
+ * RANK: no collective, a communicator is not used (tmx_argmin keeps its meaning over the whole batch and all ranks).             */
+TMX_API tmx_status tmx_argmin_queries(tmx_ctx* ctx, int64_t* best_index /* Q, -1: none converged */, double* best_cost /* Q */);
+/* The winning trajectory of every query (the rule of tmx_argmin_queries, evaluated by this call): x_out[Q][T*D], gathered on the
+ * device and copied once; the rows of queries without a converged seed are zero and found[q] (optional) = 0.  Local to the rank.  */
+TMX_API tmx_status tmx_best_trajectories(tmx_ctx* ctx, double* x_out /* Q x T x D */, int32_t* found /* Q, optional */);
 /* ... or let the library own its communicator: rank 0 calls tmx_nccl_unique_id and ships the 128 bytes to the other ranks by
  * any means (bench.py: torch.distributed broadcast); every rank then calls tmx_nccl_init (ncclCommInitRank on the context's
  * device and stream).  The communicator is destroyed with the context.                                           */

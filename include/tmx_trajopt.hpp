@@ -1523,6 +1523,12 @@ public:
       printAndThrow("must initialize before optimizing");
     const tmx_sqp_params p = param_.toTmx();
     check(tmx_problem_upload(ctx_, &prob_->desc(), &p, &osqp_));
+    if (n_queries_ > 1)  // (before tmx_batch_set_x0: it runs the first exact evaluation)
+    {
+      check(tmx_queries_set(ctx_, n_queries_));
+      for (const auto& qt : query_targets_)
+        check(tmx_query_set_targets(ctx_, qt.term, qt.values.data(), qt.len));
+    }
     check(tmx_batch_set_x0(ctx_, seeds_.data(), batch_));
     if (iteration_callbacks_.empty() && results_callbacks_.empty())
       check(tmx_sqp_run(ctx_, 0, nullptr));
@@ -1557,8 +1563,63 @@ public:
     results_ = batch_results_[best_];
     for (auto& cb : callbacks_)
       cb(prob_.get(), results_);
+    query_best_ = QueryBest();
+    if (n_queries_ > 1)
+    {
+      const std::size_t Q = static_cast<std::size_t>(n_queries_);
+      std::vector<double> qx(Q * nv);
+      std::vector<int32_t> found(Q);
+      query_best_.index.assign(Q, -1);
+      query_best_.total_cost.assign(Q, 0.0);
+      check(tmx_argmin_queries(ctx_, query_best_.index.data(), query_best_.total_cost.data()));
+      check(tmx_best_trajectories(ctx_, qx.data(), found.data()));
+      for (std::size_t q = 0; q < Q; ++q)
+      {
+        query_best_.x.emplace_back(qx.begin() + static_cast<std::ptrdiff_t>(q * nv), qx.begin() + static_cast<std::ptrdiff_t>((q + 1) * nv));
+        query_best_.found.push_back(found[q] != 0);
+      }
+    }
     return results_.status;
   }
+
+  /** Multi-query batches (include/tmx.h: tmx_queries_set): the seeds given to initialize() are n_queries groups of equal size, ordered
+      by query; every query shares the problem and has its own goal targets (setQueryTargets).  n_queries = 1: one query, the
+      problem's own targets.  Clears the targets set so far. */
+  void setQueries(int n_queries)
+  {
+    if (n_queries < 1)
+      printAndThrow("setQueries: n_queries must be at least 1");
+    n_queries_ = n_queries;
+    query_targets_.clear();
+  }
+  /** The targets of term `term` (index into the problem's term list, TrajOptProb::desc().terms: costs first) for every query: 12
+      values (a 3 x 4 pose, row-major) for a cart-pose term, n_dof for a joint-position constraint / inequality cost.  Terms without a
+      call keep the problem's own target in every query; what the library refuses is reported by optimize(). */
+  void setQueryTargets(std::size_t term, const std::vector<DblVec>& targets)
+  {
+    if (targets.size() != static_cast<std::size_t>(n_queries_) || targets.empty())
+      printAndThrow("setQueryTargets: one target per query (call setQueries first)");
+    QueryTargets qt;
+    qt.term = static_cast<int32_t>(term);
+    qt.len = static_cast<int32_t>(targets[0].size());
+    for (const DblVec& t : targets)
+    {
+      if (t.size() != targets[0].size())
+        printAndThrow("setQueryTargets: the targets of all queries have one length");
+      qt.values.insert(qt.values.end(), t.begin(), t.end());
+    }
+    query_targets_.push_back(qt);
+  }
+  /** the best converged seed of every query after optimize() (tmx_argmin_queries / tmx_best_trajectories; local to the rank): its
+      index in the batch (-1: none converged), its cost (1e300: none), its trajectory (zeros: none) */
+  struct QueryBest
+  {
+    std::vector<int64_t> index;
+    DblVec total_cost;
+    std::vector<DblVec> x;
+    std::vector<bool> found;
+  };
+  const QueryBest& bestPerQuery() const { return query_best_; }
 
   DblVec& x() { return results_.x; }
   OptResults& results() { return results_; }
@@ -1672,6 +1733,14 @@ private:
   }
   trajopt::TrajOptProb::Ptr prob_;
   tmx_ctx* ctx_{ nullptr };
+  struct QueryTargets
+  {
+    int32_t term{ 0 }, len{ 0 };
+    std::vector<double> values;  // n_queries x len
+  };
+  int32_t n_queries_{ 1 };
+  std::vector<QueryTargets> query_targets_;
+  QueryBest query_best_;
   BasicTrustRegionSQPParameters param_;
   tmx_osqp_settings osqp_{};
   std::vector<double> seeds_;

@@ -82,6 +82,19 @@ struct tmx_ctx
   double* d_best{ nullptr };   // T * D + 1 doubles: the broadcast buffer of tmx_best_trajectory (trajectory, status word)
   size_t best_cap{ 0 };
   int max_rec{ 128 };
+  // Multi-query batches (tmx_queries_set; DevBatch::q_prob / q_cp_target / q_aux1).  n_queries = 1: no table, null pointers.
+  int n_queries{ 1 };
+  std::vector<void*> query_allocs;
+  DevProblem* d_qprob{ nullptr };
+  double *d_qcp{ nullptr }, *d_qaux1{ nullptr };
+  std::vector<double> own_cp, own_aux1;  // the description's own targets (Lowered::cp_target / aux1)
+  std::vector<int> own_sub;              // Lowered::sub (the joint of a joint-position slot)
+  std::vector<double> h_qcp, h_qaux1;    // host mirrors of the per-query tables
+  // per term of the description: its kind and its ranges of cart-pose instances and row slots (Lowered::term_*)
+  std::vector<int> term_kind, term_cp0, term_cp1, term_slot0, term_slot1;
+  int n_dof{ 0 };
+  // Bcap = 0 also says "no valid batch" (every entry point tests it): Balloc keeps the allocated capacity across an invalidation
+  int Balloc{ 0 };
 };
 
 template <typename T>
@@ -231,6 +244,7 @@ void tmx_destroy(tmx_ctx* ctx)
   (void)hipStreamSynchronize(ctx->stream);
   free_pool(ctx->prob_allocs);
   free_pool(ctx->batch_allocs);
+  free_pool(ctx->query_allocs);
   if (ctx->dp)
     (void)hipFree(ctx->dp);
   if (ctx->db)
@@ -430,6 +444,10 @@ static tmx_status lower_terms(const tmx_problem_desc* d, DevProblem& P, Lowered&
       z = z && std::fabs(tm.upper_tols[j]) < 1e-5 && std::fabs(tm.lower_tols[j]) < 1e-5;  // trajopt_common::doubleEquals (vector_ops.hpp:17)
     return z;
   };
+  L.term_cp0.assign((size_t)d->n_terms, 0);
+  L.term_cp1.assign((size_t)d->n_terms, 0);
+  L.term_slot0.assign((size_t)d->n_terms, 0);
+  L.term_slot1.assign((size_t)d->n_terms, 0);
   for (int pass = 0; pass < 5; ++pass)
     for (int k = 0; k < d->n_terms; ++k)
     {
@@ -522,6 +540,8 @@ static tmx_status lower_terms(const tmx_problem_desc* d, DevProblem& P, Lowered&
           pose_tol = pose_tol || std::fabs(tm.lower_tols[i] - tm.upper_tols[i]) > 1e-6;
         }
       const int kind_eff = (tm.kind == TMX_TERM_CART_POSE && pose_tol) ? TMX_TERM_DYN_CART_POSE : tm.kind;
+      L.term_cp0[(size_t)k] = (int)L.cp_t.size();
+      L.term_slot0[(size_t)k] = (int)L.kind.size();
       switch (kind_eff)
       {
         case TMX_TERM_JOINT_VEL_COST:
@@ -1223,6 +1243,8 @@ static tmx_status lower_terms(const tmx_problem_desc* d, DevProblem& P, Lowered&
           err = "term kind not lowered by the device path";
           return TMX_ERR_UNSUPPORTED;
       }
+      L.term_cp1[(size_t)k] = (int)L.cp_t.size();
+      L.term_slot1[(size_t)k] = (int)L.kind.size();
     }
   if (flavor == TMX_FLAVOR_SQP)
     for (int v = 0; v < P.NX; ++v)
@@ -1868,6 +1890,8 @@ static tmx_status configure_launch(tmx_ctx* ctx, const DevProblem& P, const Lowe
                                static_cast<int>(ctx->smem_chain)));
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_sqp_fused_hbm), hipFuncAttributeMaxDynamicSharedMemorySize,
                                static_cast<int>(ctx->smem_chain)));
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_sqp_fused_hbm_q), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               static_cast<int>(ctx->smem_chain)));
   }
   // one problem per CU when the workspace is large: use 4 waves so the data-parallel phases go 4x wider
   ctx->nt_qp = TMX_QP_NT;
@@ -1918,6 +1942,17 @@ static tmx_status configure_launch(tmx_ctx* ctx, const DevProblem& P, const Lowe
   return TMX_OK;
 }
 
+// back to one query: the per-query tables go and the next batch carries null pointers (ensure_batch)
+static void drop_queries(tmx_ctx* ctx)
+{
+  free_pool(ctx->query_allocs);
+  ctx->n_queries = 1;
+  ctx->d_qprob = nullptr;
+  ctx->d_qcp = ctx->d_qaux1 = nullptr;
+  ctx->h_qcp.clear();
+  ctx->h_qaux1.clear();
+}
+
 tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx_sqp_params* sqp, const tmx_osqp_settings* osqp)
 {
   if (!ctx || !d)
@@ -1962,14 +1997,27 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
   }
   free_pool(ctx->prob_allocs);
   free_pool(ctx->batch_allocs);
-  ctx->Bcap = 0;
+  ctx->Bcap = ctx->Balloc = 0;
   ctx->have_problem = false;
+  drop_queries(ctx);  // a new problem has one query
   DevProblem& P = ctx->hp;
   fill_basic_info(d, sqp, osqp, P);
   Lowered L;
   tmx_status rc;
   if ((rc = lower_terms(d, P, L, ctx->err)) != TMX_OK)
     return rc;
+  // what tmx_queries_set / tmx_query_set_targets need of the lowering
+  ctx->own_cp = L.cp_target;
+  ctx->own_aux1 = L.aux1;
+  ctx->own_sub = L.sub;
+  ctx->term_cp0 = L.term_cp0;
+  ctx->term_cp1 = L.term_cp1;
+  ctx->term_slot0 = L.term_slot0;
+  ctx->term_slot1 = L.term_slot1;
+  ctx->term_kind.resize((size_t)d->n_terms);
+  for (int k = 0; k < d->n_terms; ++k)
+    ctx->term_kind[(size_t)k] = d->terms[k].kind;
+  ctx->n_dof = DK;
   const EngineChoice E = choose_engine(L, P, hooks);
   P.band = E.band;
   P.band_rows = E.band_rows ? 1 : 0;
@@ -1987,23 +2035,40 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
 
 static tmx_status ensure_batch(tmx_ctx* ctx, int B)
 {
-  if (B <= ctx->Bcap)
+  if (ctx->n_queries > 1 && B % ctx->n_queries != 0)
   {
-    // (stream-ordered and only when the batch size changes: a synchronous copy is a null-stream operation, which waits for
-    //  every other blocking stream of the device - i.e. for the other context's batch still in flight)
-    if (ctx->hb.B != B)
+    ctx->err = "tmx_batch_set_x0: the batch must hold the same number of seeds for each of the " + std::to_string(ctx->n_queries) +
+               " queries (batch % n_queries == 0)";
+    return TMX_ERR_INVALID;
+  }
+  const int spq = ctx->n_queries > 1 ? B / ctx->n_queries : 0;  // (one query: 0 and null tables)
+  if (B <= ctx->Balloc)
+  {
+    // (stream-ordered and only when the batch size or the query tables change: a synchronous copy is a null-stream operation, which
+    //  waits for every other blocking stream of the device - i.e. for the other context's batch still in flight)
+    if (ctx->hb.B != B || ctx->hb.seeds_per_query != spq || ctx->hb.q_prob != ctx->d_qprob)
     {
       ctx->hb.B = B;
+      ctx->hb.seeds_per_query = spq;
+      ctx->hb.q_prob = ctx->d_qprob;
+      ctx->hb.q_cp_target = ctx->d_qcp;
+      ctx->hb.q_aux1 = ctx->d_qaux1;
       HIPCHK(hipMemcpyAsync(ctx->db, &ctx->hb, sizeof(DevBatch), hipMemcpyHostToDevice, ctx->stream));
       HIPCHK(hipStreamSynchronize(ctx->stream));  // hb is host memory that the next call may modify
     }
+    ctx->Bcap = ctx->Balloc;  // (valid again after an invalidation by tmx_queries_set / tmx_query_set_targets)
     return TMX_OK;
   }
   free_pool(ctx->batch_allocs);
+  ctx->Bcap = ctx->Balloc = 0;
   const DevProblem& P = ctx->hp;
   DevBatch& H = ctx->hb;
   std::memset(&H, 0, sizeof(H));
   H.B = B;
+  H.seeds_per_query = spq;
+  H.q_prob = ctx->d_qprob;
+  H.q_cp_target = ctx->d_qcp;
+  H.q_aux1 = ctx->d_qaux1;
   H.max_rec = ctx->max_rec;
   auto& pool = ctx->batch_allocs;
   tmx_status rc;
@@ -2146,7 +2211,7 @@ static tmx_status ensure_batch(tmx_ctx* ctx, int B)
     ctx->db = static_cast<DevBatch*>(p);
   }
   HIPCHK(hipMemcpy(ctx->db, &H, sizeof(DevBatch), hipMemcpyHostToDevice));
-  ctx->Bcap = B;
+  ctx->Bcap = ctx->Balloc = B;
   return TMX_OK;
 }
 
@@ -2252,7 +2317,9 @@ tmx_status tmx_sqp_launch(tmx_ctx* ctx)
   }
   if (ctx->timing)
     HIPCHK(hipEventRecord(ctx->ev0, ctx->stream));
-  if (ctx->ws_in_hbm)
+  if (ctx->ws_in_hbm && ctx->n_queries > 1)  // (the one-query kernel carries no multi-query code: sqp_step_block<.., MQ>)
+    TMX_LAUNCH(k_sqp_fused_hbm_q, B, ctx->nt_qp > 1 ? TMX_HBM_NT : 1, ctx->smem_chain, ctx->stream, ctx->dp, ctx->db, 0);
+  else if (ctx->ws_in_hbm)
     TMX_LAUNCH(k_sqp_fused_hbm, B, ctx->nt_qp > 1 ? TMX_HBM_NT : 1, ctx->smem_chain, ctx->stream, ctx->dp, ctx->db, 0);
 #if TMX_IS_DEVICE
   else if (ctx->wave && ctx->mode == 2)
@@ -2369,7 +2436,10 @@ tmx_status tmx_sqp_run(tmx_ctx* ctx, int32_t max_steps, int32_t* n_active_out)
   }
   if (ctx->mode != 0)
   {
-    if (ctx->ws_in_hbm)
+    if (ctx->ws_in_hbm && ctx->n_queries > 1)
+      TIMED(ctx->ms_admm, ctx->launches_admm++,
+            TMX_LAUNCH(k_sqp_fused_hbm_q, B, ctx->nt_qp > 1 ? TMX_HBM_NT : 1, ctx->smem_chain, ctx->stream, ctx->dp, ctx->db, (int)max_steps));
+    else if (ctx->ws_in_hbm)
       TIMED(ctx->ms_admm, ctx->launches_admm++,
             TMX_LAUNCH(k_sqp_fused_hbm, B, ctx->nt_qp > 1 ? TMX_HBM_NT : 1, ctx->smem_chain, ctx->stream, ctx->dp, ctx->db, (int)max_steps));
     else
@@ -3210,6 +3280,207 @@ tmx_status tmx_best_trajectory(tmx_ctx* ctx, double* x_out, int32_t* owner_rank)
   return TMX_OK;
 }
 
+// ---- multi-query batches (include/tmx.h) ----
+
+// the Q copies of the DevProblem: the uploaded one with cp_target / slot_aux1 pointing at the query's tables (DevBatch::q_prob)
+static tmx_status sync_query_problems(tmx_ctx* ctx)
+{
+  if (ctx->n_queries <= 1 || !ctx->d_qprob)
+    return TMX_OK;
+  std::vector<DevProblem> qp((size_t)ctx->n_queries, ctx->hp);
+  for (int q = 0; q < ctx->n_queries; ++q)
+  {
+    qp[(size_t)q].cp_target = ctx->d_qcp + (size_t)q * ctx->hp.n_cp * 12;
+    qp[(size_t)q].slot_aux1 = ctx->d_qaux1 + (size_t)q * ctx->hp.R;
+  }
+  HIPCHK(hipMemcpy(ctx->d_qprob, qp.data(), qp.size() * sizeof(DevProblem), hipMemcpyHostToDevice));
+  return TMX_OK;
+}
+
+// the current batch was prepared (first exact evaluation) with other targets: nothing runs or reads it until the next tmx_batch_set_x0*
+static void invalidate_batch(tmx_ctx* ctx) { ctx->Bcap = 0; }
+
+tmx_status tmx_queries_set(tmx_ctx* ctx, int32_t n_queries)
+{
+  if (!ctx)
+    return TMX_ERR_INVALID;
+  if (n_queries < 1)
+  {
+    ctx->err = "tmx_queries_set: n_queries must be at least 1";
+    return TMX_ERR_INVALID;
+  }
+  if (!ctx->have_problem)
+  {
+    ctx->err = "tmx_queries_set: no problem uploaded (call tmx_problem_upload first)";
+    return TMX_ERR_STATE;
+  }
+  TMX_REFUSE_WHILE_PENDING(ctx);
+  if (n_queries >= 2 && ctx->hp.flavor == TMX_FLAVOR_SQP)
+  {
+    ctx->err = "tmx_queries_set: multi-query batches are not lowered for TMX_FLAVOR_SQP problems (the trajopt_sqp term code reads the "
+               "targets through code of its own)";
+    return TMX_ERR_UNSUPPORTED;
+  }
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  invalidate_batch(ctx);
+  drop_queries(ctx);
+  if (n_queries == 1)
+    return TMX_OK;
+  const size_t Q = (size_t)n_queries, ncp = (size_t)ctx->hp.n_cp * 12, R = (size_t)ctx->hp.R;
+  ctx->h_qcp.resize(Q * ncp);
+  ctx->h_qaux1.resize(Q * R);
+  for (size_t q = 0; q < Q; ++q)
+  {
+    std::copy(ctx->own_cp.begin(), ctx->own_cp.begin() + (std::ptrdiff_t)ncp, ctx->h_qcp.begin() + (std::ptrdiff_t)(q * ncp));
+    std::copy(ctx->own_aux1.begin(), ctx->own_aux1.begin() + (std::ptrdiff_t)R, ctx->h_qaux1.begin() + (std::ptrdiff_t)(q * R));
+  }
+  tmx_status rc;
+  if ((rc = upload(ctx, ctx->query_allocs, &ctx->d_qcp, ctx->h_qcp)) != TMX_OK || (rc = upload(ctx, ctx->query_allocs, &ctx->d_qaux1, ctx->h_qaux1)) != TMX_OK ||
+      (rc = dalloc(ctx, ctx->query_allocs, &ctx->d_qprob, Q, false)) != TMX_OK)
+  {
+    drop_queries(ctx);
+    return rc;
+  }
+  ctx->n_queries = n_queries;
+  if ((rc = sync_query_problems(ctx)) != TMX_OK)
+    drop_queries(ctx);
+  return rc;
+}
+
+tmx_status tmx_query_set_targets(tmx_ctx* ctx, int32_t term, const double* targets, int32_t len)
+{
+  if (!ctx)
+    return TMX_ERR_INVALID;
+  if (!ctx->have_problem)
+  {
+    ctx->err = "tmx_query_set_targets: no problem uploaded (call tmx_problem_upload first)";
+    return TMX_ERR_STATE;
+  }
+  TMX_REFUSE_WHILE_PENDING(ctx);
+  if (ctx->n_queries < 2)
+  {
+    ctx->err = "tmx_query_set_targets: the context has one query (call tmx_queries_set with n_queries >= 2 first)";
+    return TMX_ERR_STATE;
+  }
+  if (!targets || term < 0 || term >= (int32_t)ctx->term_kind.size())
+  {
+    ctx->err = "tmx_query_set_targets: term index outside tmx_problem_desc::terms (or targets == NULL)";
+    return TMX_ERR_INVALID;
+  }
+  const int kind = ctx->term_kind[(size_t)term];
+  const int cp0 = ctx->term_cp0[(size_t)term], cp1 = ctx->term_cp1[(size_t)term];
+  const int s0 = ctx->term_slot0[(size_t)term], s1 = ctx->term_slot1[(size_t)term];
+  const bool pose = kind == TMX_TERM_CART_POSE;
+  const bool jpos = kind == TMX_TERM_JOINT_POS_EQ_CNT || kind == TMX_TERM_JOINT_POS_INEQ_CNT || kind == TMX_TERM_JOINT_POS_INEQ_COST;
+  if (pose && cp1 == cp0)
+  {
+    ctx->err = "tmx_query_set_targets: this cart_pose term was lowered as a function term (tolerance band): its target is a constant of "
+               "the program table (fx_consts), not a per-query target";
+    return TMX_ERR_UNSUPPORTED;
+  }
+  if (kind == TMX_TERM_JOINT_POS_EQ_COST)
+  {
+    ctx->err = "tmx_query_set_targets: the target of a squared joint_pos cost is baked into the static objective (pq), not a per-query target";
+    return TMX_ERR_UNSUPPORTED;
+  }
+  if (!pose && !jpos)
+  {
+    ctx->err = "tmx_query_set_targets: this term kind carries no per-query target (accepted: cart_pose lowered into cart-pose instances, "
+               "joint_pos equality / inequality constraints, joint_pos inequality cost)";
+    return TMX_ERR_UNSUPPORTED;
+  }
+  const int want = pose ? 12 : ctx->n_dof;
+  if (len != want)
+  {
+    ctx->err = "tmx_query_set_targets: len must be " + std::to_string(want) + " for this term (" + (pose ? "tmx_term::target_pose" : "tmx_term::targets, n_dof") + ")";
+    return TMX_ERR_INVALID;
+  }
+  const size_t Q = (size_t)ctx->n_queries;
+  for (size_t i = 0; i < Q * (size_t)len; ++i)
+    if (!std::isfinite(targets[i]))
+    {
+      ctx->err = "tmx_query_set_targets: non-finite target value";
+      return TMX_ERR_INVALID;
+    }
+  HIPCHK(hipSetDevice(ctx->device));
+  invalidate_batch(ctx);
+  const size_t ncp = (size_t)ctx->hp.n_cp * 12, R = (size_t)ctx->hp.R;
+  if (pose)
+  {
+    for (size_t q = 0; q < Q; ++q)
+      for (int c = cp0; c < cp1; ++c)  // (one instance per step of the term: the target applies to every step)
+        std::copy(targets + q * 12, targets + q * 12 + 12, ctx->h_qcp.begin() + (std::ptrdiff_t)(q * ncp + (size_t)c * 12));
+    HIPCHK(hipMemcpyAsync(ctx->d_qcp, ctx->h_qcp.data(), ctx->h_qcp.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  }
+  else
+  {
+    // the term's slots are SLOT_JOINTPOS / SLOT_JOINTPOS_INEQ rows: slot_sub = the joint
+    for (size_t q = 0; q < Q; ++q)
+      for (int r = s0; r < s1; ++r)
+        ctx->h_qaux1[q * R + (size_t)r] = targets[q * (size_t)len + (size_t)ctx->own_sub[(size_t)r]];
+    HIPCHK(hipMemcpyAsync(ctx->d_qaux1, ctx->h_qaux1.data(), ctx->h_qaux1.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  }
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return TMX_OK;
+}
+
+// the per-query reduction (k_argmin_queries); with x_out also the gather of the winning trajectories
+static tmx_status argmin_queries(tmx_ctx* ctx, int64_t* best_index, double* best_cost, double* x_out, int32_t* found)
+{
+  if (ctx->Bcap == 0)
+    return TMX_ERR_STATE;
+  TMX_REFUSE_WHILE_PENDING(ctx);
+  HIPCHK(hipSetDevice(ctx->device));
+  const int Q = ctx->n_queries, S = ctx->hb.B / Q, NX = ctx->hp.NX;
+  struct PoolGuard
+  {
+    std::vector<void*> pool;
+    ~PoolGuard() { free_pool(pool); }
+  } guard;
+  double *d_cost = nullptr, *d_x = nullptr;
+  long long* d_idx = nullptr;
+  tmx_status rc;
+  if ((rc = dalloc(ctx, guard.pool, &d_cost, (size_t)Q, false)) != TMX_OK || (rc = dalloc(ctx, guard.pool, &d_idx, (size_t)Q, false)) != TMX_OK ||
+      (x_out && (rc = dalloc(ctx, guard.pool, &d_x, (size_t)Q * NX, false)) != TMX_OK))
+    return rc;
+  const int conv = ctx->hp.flavor == TMX_FLAVOR_SQP ? (int)TMX_SQP_CONVERGED : (int)TMX_OPT_CONVERGED;
+  [[maybe_unused]] const int nt = ctx->nt_qp > 1 ? 256 : 1;  // (the host build runs a workgroup as one thread)
+  TMX_LAUNCH(k_argmin_queries, Q, nt, 16 * sizeof(double) + 18 * sizeof(int), ctx->stream, ctx->db, conv, S, NX, d_cost, d_idx, d_x);
+  HIPCHK(hipGetLastError());
+  std::vector<long long> idx((size_t)Q);
+  std::vector<double> cost((size_t)Q);
+  HIPCHK(hipMemcpyAsync(idx.data(), d_idx, sizeof(long long) * (size_t)Q, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipMemcpyAsync(cost.data(), d_cost, sizeof(double) * (size_t)Q, hipMemcpyDeviceToHost, ctx->stream));
+  if (x_out)
+    HIPCHK(hipMemcpyAsync(x_out, d_x, sizeof(double) * (size_t)Q * NX, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  for (int q = 0; q < Q; ++q)
+  {
+    if (best_index)
+      best_index[q] = idx[(size_t)q];
+    if (best_cost)
+      best_cost[q] = cost[(size_t)q];
+    if (found)
+      found[q] = idx[(size_t)q] >= 0 ? 1 : 0;
+  }
+  return TMX_OK;
+}
+
+tmx_status tmx_argmin_queries(tmx_ctx* ctx, int64_t* best_index, double* best_cost)
+{
+  if (!ctx || !best_index || !best_cost)
+    return TMX_ERR_INVALID;
+  return argmin_queries(ctx, best_index, best_cost, nullptr, nullptr);
+}
+
+tmx_status tmx_best_trajectories(tmx_ctx* ctx, double* x_out, int32_t* found)
+{
+  if (!ctx || !x_out)
+    return TMX_ERR_INVALID;
+  return argmin_queries(ctx, nullptr, nullptr, x_out, found);
+}
+
 tmx_status tmx_nccl_unique_id(uint8_t id[TMX_NCCL_UNIQUE_ID_BYTES])
 {
   if (!id)
@@ -3355,7 +3626,7 @@ __attribute__((visibility("default"))) tmx_status tmx_debug_set_flags(tmx_ctx* c
   HIPCHK(hipSetDevice(ctx->device));
   ctx->hp.dbg_flags = flags;
   HIPCHK(hipMemcpy(reinterpret_cast<char*>(ctx->dp) + offsetof(DevProblem, dbg_flags), &flags, sizeof(int), hipMemcpyHostToDevice));
-  return TMX_OK;
+  return sync_query_problems(ctx);  // (the per-query copies of the DevProblem carry the switches too)
 }
 
 // debug hook (not in include/tmx.h): 1 when the uploaded problem qualifies for the register-resident QP setup of the dense fast path

@@ -19,6 +19,7 @@ TMX_DEVFN void prepare_body(const DevProblem* P, const DevBatch* Bt)
 {
   TMX_SMEM(smem);
   const int b = blockIdx.x, tid = threadIdx.x, NT = blockDim.x;
+  P = query_problem(P, Bt, b);  // (the first exact evaluation reads the goal targets of b's query)
   const int NX = P->NX, D = P->D, R = P->R;
   const double* x0 = Bt->x0 + (size_t)b * NX;
   double* x = Bt->x + (size_t)b * NX;
@@ -109,6 +110,7 @@ TMX_DEVFN void evaluate_body(const DevProblem* P, const DevBatch* Bt, int which)
   const int b = blockIdx.x, tid = threadIdx.x, NT = blockDim.x;
   if (which == 1 && Bt->phase[b] == PHASE_DONE)
     return;
+  P = query_problem(P, Bt, b);
   const double* xv = (which ? Bt->xnew : Bt->x) + (size_t)b * P->NX;
   double* co = (which ? Bt->new_cost_vals : Bt->cost_vals) + (size_t)b * P->n_costs;
   double* vo = (which ? Bt->new_cnt_viols : Bt->cnt_viols) + (size_t)b * P->n_cnts;
@@ -137,6 +139,7 @@ TMX_DEVFN void convexify_body(const DevProblem* P, const DevBatch* Bt, int force
   TMX_SMEM(smem_lds);
   double* smem = TMX_WORK(smem_lds, Bt);
   const int b = blockIdx.x, tid = threadIdx.x, NT = blockDim.x;
+  P = query_problem(P, Bt, b);
   if (!force && P->sqp.max_time < 1e300)
   {
     if (tid == 0)
@@ -402,9 +405,14 @@ TMX_KERNEL k_sqp_update(const DevProblem* P, const DevBatch* Bt)
 
 // One trust-region evaluation of problem b: [convexify + QP structure] -> Model::optimize -> exact re-evaluation ->
 // accept / shrink / penalty decisions.  All state lives in HBM between calls.
-template <bool HBM = false, bool BANDK = true>
+// MQ = false: an instantiation without the multi-query branches (k_sqp_fused_hbm: the two call sites alone moved its allocation from
+// 883 to 3014 spilled VGPRs, so batches with queries run its twin k_sqp_fused_hbm_q and the one-query kernel is the code it was)
+template <bool HBM = false, bool BANDK = true, bool MQ = true>
 TMX_DEVFN void sqp_step_block(const DevProblem* P, const DevBatch* Bt, int b, double* smem, int tid, int NT, double* chain_lds = nullptr)
 {
+  // MULTI-QUERY BATCHES (DevBatch::q_prob): only the convexification and the exact evaluation read goal targets.  The specialised
+  // ones select the DevProblem of b's query inside their out-of-line functions (tmx_step.h), the generic ones run out of line on it
+  // (tmx_solve.h: *_query_nl) - P itself stays the kernel argument, and the code of a one-query batch is what it was.
   const int R = P->R, D = P->D, NX = P->NX;
   int* act = Bt->active + (size_t)b * R;
   double* coef = Bt->coef + (size_t)b * R * D;
@@ -436,12 +444,29 @@ TMX_DEVFN void sqp_step_block(const DevProblem* P, const DevBatch* Bt, int b, do
       TMX_ASM_OPAQUE_SGPR(lds_off);
       convexify_fast_nl(P, Bt, b, lds_off);
 #else
-      convexify_fast(P, x, act, coef, rhs, smem, tid);
+      convexify_fast(query_problem(P, Bt, b), x, act, coef, rhs, smem, tid);
 #endif
     }
     else
 #endif
+#if TMX_IS_DEVICE && TMX_ADMM_OUTLINED
+    if (MQ && TMX_UNI_B(Bt->q_prob != nullptr))
+    {
+      unsigned long long sm = (unsigned long long)(size_t)smem;
+      if (!HBM)
+      {
+        unsigned lds_off = (unsigned)(size_t)smem;  // (opaque: see the call of qp_admm_fast_nl)
+        TMX_ASM_OPAQUE_SGPR(lds_off);
+        sm = lds_off;
+      }
+      convexify_terms_query_nl<!HBM>(P, Bt, b, sm, NT);
+    }
+    else
       convexify_terms(P, x, act, coef, Bt->coef2 + (size_t)b * P->n_link * D, rhs, smem, tid, NT, Bt->rowc + (size_t)b * R, Bt->qdyn + (size_t)b * NX);
+#else
+      convexify_terms(query_problem(P, Bt, b), x, act, coef, Bt->coef2 + (size_t)b * P->n_link * D, rhs, smem, tid, NT, Bt->rowc + (size_t)b * R,
+                      Bt->qdyn + (size_t)b * NX);
+#endif
 #ifdef TMX_PROFILE
     if (tid == 0)
     {
@@ -500,7 +525,23 @@ TMX_DEVFN void sqp_step_block(const DevProblem* P, const DevBatch* Bt, int b, do
   if (!merged)
 #endif
   {
-    evaluate_terms(P, xn, Bt->new_cost_vals + (size_t)b * P->n_costs, Bt->new_cnt_viols + (size_t)b * P->n_cnts, smem, tid, NT);
+#if TMX_IS_DEVICE && TMX_ADMM_OUTLINED
+    if (MQ && TMX_UNI_B(Bt->q_prob != nullptr))
+    {
+      unsigned long long sm = (unsigned long long)(size_t)smem;
+      if (!HBM)
+      {
+        unsigned lds_off = (unsigned)(size_t)smem;  // (opaque: see the call of qp_admm_fast_nl)
+        TMX_ASM_OPAQUE_SGPR(lds_off);
+        sm = lds_off;
+      }
+      evaluate_terms_query_nl<!HBM>(P, Bt, b, sm, NT);
+    }
+    else
+      evaluate_terms(P, xn, Bt->new_cost_vals + (size_t)b * P->n_costs, Bt->new_cnt_viols + (size_t)b * P->n_cnts, smem, tid, NT);
+#else
+    evaluate_terms(query_problem(P, Bt, b), xn, Bt->new_cost_vals + (size_t)b * P->n_costs, Bt->new_cnt_viols + (size_t)b * P->n_cnts, smem, tid, NT);
+#endif
     TMX_F5_TICK(13);
   }
 #if TMX_IS_DEVICE
@@ -513,7 +554,7 @@ TMX_DEVFN void sqp_step_block(const DevProblem* P, const DevBatch* Bt, int b, do
 #else
     if (merged)
     {
-      step_eval_fast(P, Bt, b, smem, tid);
+      step_eval_fast(query_problem(P, Bt, b), Bt, b, smem, tid);
       TMX_F5_TICK(13);  // (exact evaluation and model values; slot 14 stays empty)
     }
     sqp_update_fast(P, Bt, b, smem, tid, merged TMX_F5_ARGS(&tp0, Bt->prof + (size_t)b * 16));
@@ -580,7 +621,8 @@ TMX_KERNEL_LB2(TMX_HBM_NT, 1) k_qp_solve_hbm(const DevProblem* P, const DevBatch
 }
 // (one kernel for problems with and without a banded objective: the split that pays for k_sqp_pool - qp_solve_block<.., BANDK> -
 //  cost config 3 4.5 % here on one box, the register allocation of the pair-row instantiations moves with it)
-TMX_KERNEL_LB2(TMX_HBM_NT, 1) k_sqp_fused_hbm(const DevProblem* P, const DevBatch* Bt, int max_steps)
+template <bool MQ>
+TMX_DEVFN void sqp_fused_hbm_body(const DevProblem* P, const DevBatch* Bt, int max_steps)
 {
   const int b = blockIdx.x, tid = threadIdx.x, NT = blockDim.x;
   double* work = Bt->ws_hbm + (size_t)b * (size_t)Bt->ws_hbm_stride;
@@ -590,9 +632,12 @@ TMX_KERNEL_LB2(TMX_HBM_NT, 1) k_sqp_fused_hbm(const DevProblem* P, const DevBatc
   {
     if (Bt->phase[b] == PHASE_DONE)
       break;
-    sqp_step_block<true>(P, Bt, b, work, tid, NT, chain_lds);
+    sqp_step_block<true, true, MQ>(P, Bt, b, work, tid, NT, chain_lds);
   }
 }
+TMX_KERNEL_LB2(TMX_HBM_NT, 1) k_sqp_fused_hbm(const DevProblem* P, const DevBatch* Bt, int max_steps) { sqp_fused_hbm_body<false>(P, Bt, max_steps); }
+// ... for a multi-query batch (DevBatch::q_prob)
+TMX_KERNEL_LB2(TMX_HBM_NT, 1) k_sqp_fused_hbm_q(const DevProblem* P, const DevBatch* Bt, int max_steps) { sqp_fused_hbm_body<true>(P, Bt, max_steps); }
 
 // Persistent pool: gridDim.x resident workgroups repeatedly CLAIM the least-advanced ready problem, advance it by one
 // trust-region evaluation and release it.  A batch of 1024 seeds on 256 CUs has only ~4 problems per CU and their run
@@ -870,6 +915,81 @@ TMX_KERNEL k_argmin(const DevBatch* Bt, int converged_code, long long global_off
     out[0] = bc;
     out[1] = (bi >= 0) ? (double)(global_offset + bi) : -1.0;
   }
+}
+
+// the better of two (cost, index) pairs under k_argmin's rule: the lower cost, on equal costs the lower index; index -1 = no seed
+TMX_DEVFN void argmin_take(double& bc, int& bi, double c, int i)
+{
+  const bool better = i >= 0 && (c < bc || (c == bc && (bi < 0 || i < bi)));
+  bc = better ? c : bc;
+  bi = better ? i : bi;
+}
+#if TMX_IS_DEVICE
+// ... over the 64 lanes of a wave: six butterfly exchanges, every lane ends with the wave's pair
+TMX_DEVFN void argmin_wave(double& bc, int& bi)
+{
+  const int lane = threadIdx.x & 63;
+  for (int m = 1; m < 64; m <<= 1)
+  {
+    const double c = __shfl(bc, lane ^ m, 64);
+    const int i = __shfl(bi, lane ^ m, 64);
+    argmin_take(bc, bi, c, i);
+  }
+}
+#endif
+// K7 per query (tmx_argmin_queries / tmx_best_trajectories): workgroup q reduces (total_cost, index) over the S problems of query q
+// with k_argmin's rule - a strided pass per thread, a butterfly per wave, one pair per wave through LDS, a butterfly of the first wave
+// over those - and, with x_out, copies the winning trajectory to x_out[q] (zeros when no seed of the query converged).
+// out_cost[q] = cost (1e300: none), out_index[q] = index in the batch (-1: none).  LDS: 16 doubles + 17 ints.
+TMX_KERNEL k_argmin_queries(const DevBatch* Bt, int converged_code, int S, int NX, double* out_cost, long long* out_index, double* x_out)
+{
+  TMX_SMEM(smem);
+  const int q = blockIdx.x, tid = threadIdx.x, NT = blockDim.x;
+  double bc = 1e300;
+  int bi = -1;
+  for (int s = tid; s < S; s += NT)  // (ascending indices per thread: the strict comparison keeps the lowest index of equal costs)
+  {
+    const int b = q * S + s;
+    if (Bt->status[b] == converged_code && Bt->total_cost[b] < bc)
+    {
+      bc = Bt->total_cost[b];
+      bi = b;
+    }
+  }
+  [[maybe_unused]] double* wc = smem;           // [16] the waves' costs
+  int* wi = reinterpret_cast<int*>(smem + 16);  // [16] the waves' indices, [16] = the winner
+#if TMX_IS_DEVICE
+  if (NT > 1)
+  {
+    const int lane = tid & 63, wv = tid >> 6, nw = (NT + 63) >> 6;
+    argmin_wave(bc, bi);
+    if (lane == 0)
+    {
+      wc[wv] = bc;
+      wi[wv] = bi;
+    }
+    TMX_SYNC();
+    if (wv == 0)
+    {
+      bc = lane < nw ? wc[lane] : 1e300;
+      bi = lane < nw ? wi[lane] : -1;
+      argmin_wave(bc, bi);
+    }
+  }
+#endif
+  if (tid == 0)
+  {
+    out_cost[q] = bc;
+    out_index[q] = bi;
+    wi[16] = bi;
+  }
+  if (x_out == nullptr)
+    return;
+  TMX_SYNC();
+  const int win = wi[16];
+  const double* src = Bt->x + (size_t)(win < 0 ? 0 : win) * NX;
+  for (int v = tid; v < NX; v += NT)
+    x_out[(size_t)q * NX + v] = win < 0 ? 0.0 : src[v];
 }
 
 // number of problems not DONE + running totals; `totals` = {n_active, n_fe, n_qp, admm} zeroed by the host first

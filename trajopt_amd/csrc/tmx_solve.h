@@ -3533,3 +3533,41 @@ TMX_DEVFN void sqp2_update_block(const DevProblem* P, const DevBatch* Bt, int b,
   }
 }
 #endif
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// MULTI-QUERY BATCHES (DevBatch::q_prob) in the fused kernels: the generic convexification and exact evaluation of a step on the
+// DevProblem of b's query, as functions of their own.  The fused kernels (k_sqp_pool at 512 VGPRs with spills) keep their one-query
+// code as it was - the problem pointer there is the kernel argument, whose loads the compiler knows to be global and uniform; a
+// pointer selected inside the kernel moved its whole allocation - and enter these only when the batch carries queries.  LDS: `smem_in`
+// is the workgroup's LDS offset (as in the other out-of-line functions), otherwise the address of its HBM workspace.
+// ---------------------------------------------------------------------------------------------------------------------------
+#if TMX_IS_DEVICE && TMX_ADMM_OUTLINED
+template <bool LDS>
+TMX_DEVFN double* tmx_query_scratch(unsigned long long smem_in)
+{
+  if (LDS)
+    return (double*)(tmx_lds_d*)(size_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)smem_in);
+  return tmx_uniform_ptr((double*)smem_in);
+}
+template <bool LDS>
+__device__ __attribute__((noinline)) static void convexify_terms_query_nl(const DevProblem* P_in, const DevBatch* Bt_in, int b_in, unsigned long long smem_in, int NT_in)
+{
+  const DevBatch* Bt = tmx_uniform_ptr(Bt_in);
+  const int b = __builtin_amdgcn_readfirstlane(b_in), NT = __builtin_amdgcn_readfirstlane(NT_in);
+  const DevProblem* P = tmx_uniform_ptr(query_problem(P_in, Bt, b));
+  const int tid = threadIdx.x, R = P->R, D = P->D, NX = P->NX;
+  convexify_terms(P, Bt->x + (size_t)b * NX, Bt->active + (size_t)b * R, Bt->coef + (size_t)b * R * D, Bt->coef2 + (size_t)b * P->n_link * D,
+                  Bt->rhs + (size_t)b * R, tmx_query_scratch<LDS>(smem_in), tid, NT, Bt->rowc + (size_t)b * R, Bt->qdyn + (size_t)b * NX);
+}
+// ... of the candidate xnew -> new_cost_vals / new_cnt_viols
+template <bool LDS>
+__device__ __attribute__((noinline)) static void evaluate_terms_query_nl(const DevProblem* P_in, const DevBatch* Bt_in, int b_in, unsigned long long smem_in, int NT_in)
+{
+  const DevBatch* Bt = tmx_uniform_ptr(Bt_in);
+  const int b = __builtin_amdgcn_readfirstlane(b_in), NT = __builtin_amdgcn_readfirstlane(NT_in);
+  const DevProblem* P = tmx_uniform_ptr(query_problem(P_in, Bt, b));
+  const int tid = threadIdx.x;
+  evaluate_terms(P, Bt->xnew + (size_t)b * P->NX, Bt->new_cost_vals + (size_t)b * P->n_costs, Bt->new_cnt_viols + (size_t)b * P->n_cnts,
+                 tmx_query_scratch<LDS>(smem_in), tid, NT);
+}
+#endif

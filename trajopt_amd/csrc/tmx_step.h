@@ -334,9 +334,9 @@ __device__ __attribute__((noinline)) static void qp_structure_fast_nl(const DevP
 }
 __device__ __attribute__((noinline)) static void sqp_update_fast_nl(const DevProblem* P_in, const DevBatch* Bt_in, int b_in, unsigned lds_in)
 {
-  const DevProblem* P = tmx_uniform_ptr(P_in);
   const DevBatch* Bt = tmx_uniform_ptr(Bt_in);
   const int b = __builtin_amdgcn_readfirstlane(b_in);
+  const DevProblem* P = tmx_uniform_ptr(query_problem(P_in, Bt, b));  // (multi-query batches: the exact evaluation reads goal targets)
   const int tid = threadIdx.x;
   double* smem = (double*)(tmx_lds_d*)(size_t)(unsigned)__builtin_amdgcn_readfirstlane((int)lds_in);
   // on the problems of DevProblem::eval_fast the caller has skipped evaluate_terms: exact evaluation and model values as one pass
@@ -349,9 +349,9 @@ __device__ __attribute__((noinline)) static void sqp_update_fast_nl(const DevPro
 // the convexification of the problems of DevProblem::eval_fast (tmx_eval.h)
 __device__ __attribute__((noinline)) static void convexify_fast_nl(const DevProblem* P_in, const DevBatch* Bt_in, int b_in, unsigned lds_in)
 {
-  const DevProblem* P = tmx_uniform_ptr(P_in);
   const DevBatch* Bt = tmx_uniform_ptr(Bt_in);
   const int b = __builtin_amdgcn_readfirstlane(b_in);
+  const DevProblem* P = tmx_uniform_ptr(query_problem(P_in, Bt, b));  // (multi-query batches: the cart-pose rows read goal targets)
   const int tid = threadIdx.x;
   double* smem = (double*)(tmx_lds_d*)(size_t)(unsigned)__builtin_amdgcn_readfirstlane((int)lds_in);
   convexify_fast(P, Bt->x + (size_t)b * P->NX, Bt->active + (size_t)b * P->R, Bt->coef + (size_t)b * P->R * P->D, Bt->rhs + (size_t)b * P->R, smem, tid);

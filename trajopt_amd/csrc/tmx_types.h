@@ -261,7 +261,24 @@ struct DevBatch
   //   tv_aff: B x n_tv x T x TMX_TV_REC  - linearised rows of the squared velocity costs (record of segment t at [t])
   //   tt_aff: B x n_tt x (T + 1)         - cleaned gradient of sum_t 1 / tau[t] on tau[t] at [t] (t = 1 .. T-1), the constant at [T]
   double *tv_aff, *tt_aff;
+  // MULTI-QUERY BATCHES (tmx_queries_set: Q queries x seeds_per_query seeds, problem b belongs to query b / seeds_per_query).  The
+  // goal targets are stored per QUERY: q_cp_target (Q x n_cp x 12) and q_aux1 (Q x R, a whole copy of slot_aux1 per query).  q_prob =
+  // Q copies of the DevProblem whose cp_target / slot_aux1 point at the query's tables and whose other fields are the uploaded
+  // ones: every per-problem function selects its DevProblem ONCE (query_problem below, uniform over the workgroup), so no reader of
+  // a target knows about queries.  All three pointers are null and seeds_per_query is 0 for one query.  (Last: the offsets of
+  // the fields above are what they were.)
+  const DevProblem* q_prob;
+  double *q_cp_target, *q_aux1;
+  int seeds_per_query;
 };
+// the DevProblem of problem b: the uploaded one, or the copy of b's query (b must be uniform over the workgroup)
+TMX_DEVFN const DevProblem* query_problem(const DevProblem* P, const DevBatch* Bt, int b)
+{
+  const DevProblem* qp = Bt->q_prob;
+  if (qp != nullptr)
+    P = qp + b / Bt->seeds_per_query;
+  return P;
+}
 
 // rows of a waypoint the register-resident Ruiz scaling keeps per column (tmx_setup.h); the grouped e buffer (QpWs::hr) is padded by
 // as many entries, which is what the burst's own column cache reads (16 + 2 CJX of admm_burst_core, tmx_part.h)

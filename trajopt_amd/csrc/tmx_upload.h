@@ -29,6 +29,9 @@ struct Lowered
   std::vector<int> ls_link, ls_hull;
   std::vector<double> ls_center, ls_radius, ob_center, ob_radius, ob_axis, ls_axis, ob_box, hullv, mesh;
   std::vector<int> wp_start, wp_list;  // slots grouped by waypoint, ascending slot id inside a waypoint
+  // per term of the description (index into tmx_problem_desc::terms): the cart-pose instances [term_cp0, term_cp1) and the row
+  // slots [term_slot0, term_slot1) it was lowered into (tmx_query_set_targets writes a query's targets there)
+  std::vector<int> term_cp0, term_cp1, term_slot0, term_slot1;
   int R = 0, R2 = 0, NA = 0;           // row slots, second coefficient blocks (pair rows), penalty variables
   int n_costs = 0, n_cnts = 0;
   int n_sq = 0;

@@ -1775,7 +1775,19 @@ TMX_DEVFN void sqp_step_wave(const DevProblem* P, const DevBatch* Bt, int b, dou
   }
   if (Bt->phase[b] == PHASE_CONVEXIFY)
   {
-    convexify_terms(P, x, act, coef, Bt->coef2, rhs, smem, tid, NT, Bt->rowc + (size_t)b * R, Bt->qdyn + (size_t)b * NX);
+    // (multi-query batches: the shared term code runs out of line on the DevProblem of b's query, as in sqp_step_block)
+#if TMX_ADMM_OUTLINED
+    if (TMX_UNI_B(Bt->q_prob != nullptr))
+    {
+      unsigned lds_off = (unsigned)(size_t)smem;
+      TMX_ASM_OPAQUE_SGPR(lds_off);
+      convexify_terms_query_nl<true>(P, Bt, b, lds_off, NT);
+    }
+    else
+      convexify_terms(P, x, act, coef, Bt->coef2, rhs, smem, tid, NT, Bt->rowc + (size_t)b * R, Bt->qdyn + (size_t)b * NX);
+#else
+    convexify_terms(query_problem(P, Bt, b), x, act, coef, Bt->coef2, rhs, smem, tid, NT, Bt->rowc + (size_t)b * R, Bt->qdyn + (size_t)b * NX);
+#endif
     qp_structure(P, act, coef, Bt->coef2, rhs, x, Bt->trust[b], Bt->merit + (size_t)b * P->n_cnts, Bt->dims + 4 * b, Bt->hashes + 4 * b, nullptr,
                  reinterpret_cast<int*>(smem), tid, NT, Bt->qdyn + (size_t)b * NX, nullptr);
   }
@@ -1786,7 +1798,18 @@ TMX_DEVFN void sqp_step_wave(const DevProblem* P, const DevBatch* Bt, int b, dou
   for (int v = tid; v < NX; v += NT)
     xn[v] = xq[v];
   TMX_SYNC();
-  evaluate_terms(P, xn, Bt->new_cost_vals + (size_t)b * P->n_costs, Bt->new_cnt_viols + (size_t)b * P->n_cnts, smem, tid, NT);
+#if TMX_ADMM_OUTLINED
+  if (TMX_UNI_B(Bt->q_prob != nullptr))
+  {
+    unsigned lds_off = (unsigned)(size_t)smem;
+    TMX_ASM_OPAQUE_SGPR(lds_off);
+    evaluate_terms_query_nl<true>(P, Bt, b, lds_off, NT);
+  }
+  else
+    evaluate_terms(P, xn, Bt->new_cost_vals + (size_t)b * P->n_costs, Bt->new_cnt_viols + (size_t)b * P->n_cnts, smem, tid, NT);
+#else
+  evaluate_terms(query_problem(P, Bt, b), xn, Bt->new_cost_vals + (size_t)b * P->n_costs, Bt->new_cnt_viols + (size_t)b * P->n_cnts, smem, tid, NT);
+#endif
   sqp_update_block(P, Bt, b, smem, tid, NT);
   TMX_SYNC();
   WV_TICK(Bt, b, 7, ts);

@@ -446,6 +446,14 @@ class ProblemConstructionInfo:
         return eq + [n for ti in self.cnt_infos if is_ineq(ti) for n in self._expand_names(ti)]
 
     # -- lowering -----------------------------------------------------------------------------------
+    def term_index(self, ti) -> int:
+        """index of the tmx_term that to_desc() builds for the TermInfo `ti` (one term per TermInfo, costs before constraints):
+        the `term` argument of Context.set_query_targets"""
+        for k, t in enumerate(list(self.cost_infos) + list(self.cnt_infos)):
+            if t is ti:
+                return k
+        raise ValueError("term_index: the TermInfo is not one of this problem's cost_infos / cnt_infos")
+
     def to_desc(self) -> abi.ProblemDesc:
         rob, T, D = self.robot, self.basic_info.n_steps, self.robot.n_dof
         if D > abi.TMX_MAX_DOF:

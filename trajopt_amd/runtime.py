@@ -55,6 +55,10 @@ _SIGS = {
     "tmx_workspace_info": ([C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)], C.c_int),
     "tmx_model_values": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
     "tmx_sqp_set_loop_vars": ([C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+    "tmx_queries_set": ([C.c_void_p, C.c_int32], C.c_int),
+    "tmx_query_set_targets": ([C.c_void_p, C.c_int32, C.c_void_p, C.c_int32], C.c_int),
+    "tmx_argmin_queries": ([C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+    "tmx_best_trajectories": ([C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
 }
 ABI_SYMBOLS = tuple(_SIGS.keys())
 
@@ -92,6 +96,7 @@ class Context:
         self.h = h
         self.desc = None
         self.B = 0
+        self.Q = 1   # queries of a batch (set_queries)
 
     def close(self):
         if getattr(self, "h", None):
@@ -120,6 +125,7 @@ class Context:
         self._chk(self.lib.tmx_qp_dims(self.h, C.byref(nm), C.byref(mm)))
         self.n_max, self.m_max = nm.value, mm.value
         self.T, self.D = desc.n_steps, desc.n_dof + (1 if desc.use_time else 0)   # columns of a trajectory (joints + the time column)
+        self.Q = 1   # (a new problem has one query)
 
     # ---- S3 ----
     def set_x0(self, x0):
@@ -337,6 +343,33 @@ class Context:
         self._chk(self.lib.tmx_best_trajectory(self.h, _ptr(x), C.byref(owner)))
         return x, owner.value
 
+    # ---- multi-query batches: Q queries x S seeds, problem b belongs to query b // S ----
+    def set_queries(self, n: int):
+        """tmx_queries_set: the following batches hold n queries (n >= 2: every query starts from the description's own targets;
+        1: back to the one-query path).  Invalidates the current batch: set_x0 comes after the targets"""
+        self._chk(self.lib.tmx_queries_set(self.h, int(n)))
+        self.Q = int(n)
+
+    def set_query_targets(self, term: int, targets):
+        """tmx_query_set_targets: targets[Q][len] of term `term` (index into desc.terms): len = 12 for a cart_pose term (layout of
+        tmx_term::target_pose), n_dof for the joint_pos constraints and the joint_pos inequality cost"""
+        t = np.ascontiguousarray(targets, dtype=np.float64)
+        if t.ndim != 2 or t.shape[0] != self.Q:
+            raise TmxError(f"set_query_targets: targets must be [n_queries = {self.Q}][len], got {list(t.shape)}")
+        self._chk(self.lib.tmx_query_set_targets(self.h, int(term), _ptr(t), t.shape[1]))
+
+    def argmin_queries(self):
+        """tmx_argmin_queries: (best index in the batch [Q] (-1: no converged seed), best cost [Q] (1e300: none)); local to the rank"""
+        bi, bc = np.zeros(self.Q, np.int64), np.zeros(self.Q)
+        self._chk(self.lib.tmx_argmin_queries(self.h, _ptr(bi), _ptr(bc)))
+        return bi, bc
+
+    def best_trajectories(self):
+        """tmx_best_trajectories: (x[Q][T][D], found[Q]): the winning trajectory of every query, zeros where none converged"""
+        x, found = np.zeros((self.Q, self.T, self.D)), np.zeros(self.Q, np.int32)
+        self._chk(self.lib.tmx_best_trajectories(self.h, _ptr(x), _ptr(found)))
+        return x, found.astype(bool)
+
     def nccl_unique_id(self) -> bytes:
         buf = (C.c_uint8 * 128)()
         self._chk(self.lib.tmx_nccl_unique_id(buf))
@@ -359,10 +392,15 @@ class Context:
 
 
 class BatchedTrustRegionSQP:
+    _queries_sent = False
     """sco::BasicTrustRegionSQP for a batch of seeds (optimizers.hpp:137-194): setParameters, initialize, optimize,
     results.  `prob` is a trajopt_amd.problem.ProblemConstructionInfo (the hatched-problem description)."""
 
-    def __init__(self, pci, device: int = 0, lib_path: str = None):
+    def __init__(self, pci, device: int = 0, lib_path: str = None, queries=None):
+        """queries (optional): a list of Q >= 2 queries - the goals of a planner - each a sequence of (TermInfo of pci, target) pairs (or
+        a mapping, for TermInfo classes that are hashable; the dataclasses of trajopt_amd.problem are not).  The batch given to
+        initialize() then holds Q x S seeds ordered by query (seed b belongs to query b // S); a TermInfo a query does not list keeps
+        its own target there.  Targets: a 4x4 / 12-value pose for a CartPoseTermInfo, n_dof joint values for a JointPosTermInfo."""
         self.pci = pci
         self.ctx = Context(device, lib_path)
         self.params = abi.default_sqp_params()
@@ -370,6 +408,31 @@ class BatchedTrustRegionSQP:
         self._uploaded = False
         self._callbacks = []
         self._step_callbacks = []
+        self.queries = None
+        if queries is not None:
+            self.setQueries(queries)
+
+    def setQueries(self, queries):
+        """the goals of the following initialize() calls (None or one mapping: the description's own targets, one query)"""
+        self.queries = ([list(q.items()) if hasattr(q, "items") else list(q) for q in queries]
+                        if queries is not None and len(queries) >= 2 else None)
+        self._queries_sent = False
+
+    def _send_queries(self):
+        Q = len(self.queries)
+        self.ctx.set_queries(Q)
+        infos = []
+        for q in self.queries:
+            infos += [ti for ti, _ in q if not any(ti is u for u in infos)]
+        for ti in infos:
+            own = np.asarray(ti.target_pose, np.float64).reshape(-1)[:12] if hasattr(ti, "target_pose") else np.asarray(ti.targets, np.float64)
+            rows = [own] * Q
+            for k, q in enumerate(self.queries):
+                for key, val in q:
+                    if key is ti:
+                        rows[k] = np.asarray(val, np.float64).reshape(-1)[:len(own)]
+            self.ctx.set_query_targets(self.pci.term_index(ti), np.stack(rows))
+        self._queries_sent = True
 
     def setParameters(self, params: abi.SqpParams):
         self.params = params
@@ -388,6 +451,11 @@ class BatchedTrustRegionSQP:
             self.desc = self.pci.to_desc()
             self.ctx.upload(self.desc, self.params, self.osqp)
             self._uploaded = True
+            self._queries_sent = False
+        if self.queries is not None and not self._queries_sent:
+            self._send_queries()     # (before set_x0: it runs the first exact evaluation)
+        elif self.queries is None and self.ctx.Q != 1:
+            self.ctx.set_queries(1)
         self.ctx.set_x0(x)
 
     def addCallback(self, cb):
@@ -412,7 +480,18 @@ class BatchedTrustRegionSQP:
         for cb in self._callbacks:
             cb(b, res)
 
+    def best_per_query(self):
+        """the best converged seed of every query: dict(index [Q] in the batch (-1: none converged), total_cost [Q], x [Q][T][D], found [Q])"""
+        bi, bc = self.ctx.argmin_queries()
+        x, found = self.ctx.best_trajectories()
+        return dict(index=bi, total_cost=bc, x=x, found=found)
+
     def optimize(self):
+        """the status of every seed; with queries the pair (status of every seed, best_per_query())"""
+        status = self._optimize()
+        return status if self.queries is None else (status, self.best_per_query())
+
+    def _optimize(self):
         if not self._callbacks and not self._step_callbacks:
             self.ctx.run(0)
             return self.ctx.results()["status"]

@@ -1622,6 +1622,8 @@ static Placement place_workspace(const Lowered& L, const EngineChoice& E, const 
       const size_t gn = (size_t)dp.Lmax * D, g_doubles = (size_t)dp.P * gn * dpart_gstride((int)gn);
       pl.polish_fast = polish_fast_doubles(T, D * T, R, NA, acc + TMX_SETUP_COL) <= g_doubles ? 1 : 0;
     }
+    // the ADMM factorisation with the interior inverses inside one wave (tmx_factor.h)
+    pl.factor_fast = (pl.setup_fast && R2 == 0 && factor_fast_fits(D, T)) ? 1 : 0;
     // the specialised SQP shell (tmx_step.h): one thread per primary column with its waypoint's rows in registers, column pointers by
     // TMX_STEP_CP_PASSES wave scans; the static objective pattern of the block-tridiagonal problems; no compact lists; trajopt_sco;
     // room for the decision's copies (2 n_costs + 3 n_cnts + the log head) in the scratch of evaluate_terms behind the model values
@@ -1807,6 +1809,7 @@ static tmx_status upload_tables(tmx_ctx* ctx, const Lowered& L, const Placement&
   P.setup_fast = pl.setup_fast;
   P.polish_fast = pl.polish_fast;
   P.step_fast = pl.step_fast;
+  P.factor_fast = pl.factor_fast;
   P.eval_fast = pl.eval_fast;
   if (pl.eval_fast)
     UP(p_hash, pl.p_hash);
@@ -3617,7 +3620,8 @@ __attribute__((visibility("default"))) tmx_status tmx_debug_admm_iters(tmx_ctx* 
 // debug hook (not in include/tmx.h): diagnostic switches of the uploaded problem (DevProblem::dbg_flags); bit 0 = scalar assembly of the
 // diagonal KKT blocks instead of the MFMA one, bit 1 = generic QP setup, bit 2 = generic polish on the dense fast path, bit 3 = generic
 // SQP shell around the QP solve (qp_structure) on a problem the specialised one can take, bit 4 = the hashes of P by the loop over its
-// columns and the generic exact evaluation and model values on a problem of eval_fast
+// columns and the generic exact evaluation and model values on a problem of eval_fast, bit 5 = the generic ADMM factorisation on a
+// problem of factor_fast
 __attribute__((visibility("default"))) tmx_status tmx_debug_set_flags(tmx_ctx* ctx, int flags)
 {
   if (!ctx || !ctx->have_problem || !ctx->dp)
@@ -3645,6 +3649,15 @@ __attribute__((visibility("default"))) int tmx_debug_polish_fast(tmx_ctx* ctx)
   if (!ctx || !ctx->have_problem)
     return -1;
   return ctx->hp.polish_fast;
+}
+
+// debug hook (not in include/tmx.h): 1 when the uploaded problem qualifies for the ADMM factorisation with the interior inverses inside
+// one wave (DevProblem::factor_fast; the kernels add their own fast-path predicate), 0 when not, -1 without a problem
+__attribute__((visibility("default"))) int tmx_debug_factor_fast(tmx_ctx* ctx)
+{
+  if (!ctx || !ctx->have_problem)
+    return -1;
+  return ctx->hp.factor_fast;
 }
 
 // debug hook (not in include/tmx.h): 1 when the uploaded problem qualifies for the specialised SQP shell around the QP solve

@@ -4,6 +4,7 @@
 #include "tmx_qp.h"
 #include "tmx_setup.h"
 #include "tmx_polish.h"
+#include "tmx_factor.h"
 #include "tmx_terms.h"
 
 #if TMX_IS_DEVICE
@@ -1136,6 +1137,37 @@ __device__ __attribute__((noinline)) static void qp_polish_fast_nl(const DevProb
   TMX_PROF_LEAVE(sh);
   TMX_SYNC();
 }
+// The ADMM factorisation of the dense fast path with the interior inverses inside one wave (tmx_factor.h) as a function of its own,
+// called from the setup of qp_solve_block and from the rho update of qp_check_nl: the register rows of the elimination do not join
+// the allocation of either caller.  rho and sigma travel as arguments (the setup fills the LDS record only behind the factorisation,
+// qp_check_nl publishes the new rho when it leaves).
+TMX_DEVFN double tmx_uniform_double(double x)
+{
+  const int lo = __builtin_amdgcn_readfirstlane(__double2loint(x)), hi = __builtin_amdgcn_readfirstlane(__double2hiint(x));
+  return __hiloint2double(hi, lo);
+}
+__device__ __attribute__((noinline)) static void qp_factor_fast_nl(const DevProblem* P_in, const DevBatch* Bt_in, int b_in, unsigned lds_in, double rho_in,
+                                                                   double sigma_in)
+{
+  const DevProblem* P = tmx_uniform_ptr(P_in);
+  const DevBatch* Bt = tmx_uniform_ptr(Bt_in);
+  const int b = __builtin_amdgcn_readfirstlane(b_in);
+  const int tid = threadIdx.x;
+  double* smem = (double*)(tmx_lds_d*)(size_t)(unsigned)__builtin_amdgcn_readfirstlane((int)lds_in);
+  const int D = P->D, T = P->T, R = P->R;
+  double* scratch = Bt->qp_scratch + (size_t)b * Bt->qp_scratch_stride;
+  QpWs w;
+#if TMX_QP_COLD_IN_LDS
+  qp_ws_carve(w, smem, smem + qp_lds_doubles(D, T, R, P->NA, P->n_link), scratch, D, T, R, P->NA, P->n_link, P->coef_far);
+#else
+  qp_ws_carve(w, smem, scratch + qp_far_doubles(D, T, R, P->NA, P->n_link, P->coef_far), scratch, D, T, R, P->NA, P->n_link, P->coef_far);
+#endif
+  w.rho = tmx_uniform_double(rho_in);
+  w.sigma = tmx_uniform_double(sigma_in);
+  TMX_PROF_ENTER(0);
+  factor_fast(w, P, P->osqp.delta, tid, pc, tlast);
+  TMX_PROF_LEAVE(0);
+}
 // between two bursts (iteration `iter` just done): returns 1 when the loop ends
 // (the workgroup's dynamic LDS base travels as a 32-bit LDS offset: no extern __shared__ lookup inside the callees)
 __device__ __attribute__((noinline)) static int qp_check_nl(const DevProblem* P_in, const DevBatch* Bt_in, int b_in, int iter_in, unsigned lds_in)
@@ -1192,10 +1224,21 @@ __device__ __attribute__((noinline)) static int qp_check_nl(const DevProblem* P_
       rho = w.rho;
       info.rho_updates += 1;
       TMX_TICK(6);
-      kkt_factor(w, P, 0, w.sigma, st.delta, tid, NT);
-      kkt_invert(w, true, tid, NT, pc, tlast);
-      admm_cache_weights(w, tid, NT);
-      TMX_TICK(15);
+      // (DevProblem::dbg_flags bit 5, or bit 0 with its scalar assembly, keeps the generic factorisation: same bits)
+      if (TMX_UNI_B(P->factor_fast != 0 && !(P->dbg_flags & 33)))
+      {
+        qp_factor_fast_nl(P, Bt, b, (unsigned)__builtin_amdgcn_readfirstlane((int)lds_in), w.rho, w.sigma);
+#ifdef TMX_PROFILE
+        tlast = TMX_CLK();
+#endif
+      }
+      else
+      {
+        kkt_factor(w, P, 0, w.sigma, st.delta, tid, NT);
+        kkt_invert(w, true, tid, NT, pc, tlast);
+        admm_cache_weights(w, tid, NT);
+        TMX_TICK(15);
+      }
     }
   }
   TMX_SYNC();
@@ -2094,12 +2137,32 @@ TMX_DEVFN void qp_solve_block(const DevProblem* P, const DevBatch* Bt, int b, do
   if (fast)
     qp_ws_alias_deltas(w, P, dpt);
 #endif
-  kkt_factor(w, P, 0, w.sigma, st.delta, tid, NT);
-  kkt_invert(w, fast, tid, NT, pc, tlast);
-  if (w.ttn > 0)
-    tt_factor(w, tid, NT);
-  admm_cache_weights(w, tid, NT);
-  TMX_TICK(15);
+#if TMX_IS_DEVICE
+  // the dense fast path: the interior inverses inside one wave (tmx_factor.h).  DevProblem::dbg_flags bit 5 (or bit 0: the scalar
+  // assembly) keeps the generic factorisation below: same bits
+  if (TMX_UNI_B(fast && P->factor_fast != 0 && !(P->dbg_flags & 33)))
+  {
+#if TMX_ADMM_OUTLINED
+    unsigned lds_off = (unsigned)(size_t)smem;  // (opaque: see the call of qp_admm_fast_nl below)
+    TMX_ASM_OPAQUE_SGPR(lds_off);
+    qp_factor_fast_nl(P, Bt, b, lds_off, w.rho, w.sigma);
+#ifdef TMX_PROFILE
+    tlast = TMX_CLK();
+#endif
+#else
+    factor_fast(w, P, st.delta, tid, pc, tlast);
+#endif
+  }
+  else
+#endif
+  {
+    kkt_factor(w, P, 0, w.sigma, st.delta, tid, NT);
+    kkt_invert(w, fast, tid, NT, pc, tlast);
+    if (w.ttn > 0)
+      tt_factor(w, tid, NT);
+    admm_cache_weights(w, tid, NT);
+    TMX_TICK(15);
+  }
   QpInfo info;
   info.status = 11;  // OSQP_UNSOLVED
   info.iter = 0;

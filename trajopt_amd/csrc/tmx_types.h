@@ -156,7 +156,8 @@ struct DevProblem
   // bit 2 = the generic polish on such a problem (polish_fast below);
   // bit 3 = the generic SQP shell around the QP solve (qp_structure) on a problem the specialised one can take (step_fast below);
   // bit 4 = the hashes of P by the loop over its columns and the generic exact evaluation and model values (evaluate_terms,
-  //         sqp_model_values) on a problem that qualifies for the table and the merged evaluation (eval_fast below)
+  //         sqp_model_values) on a problem that qualifies for the table and the merged evaluation (eval_fast below);
+  // bit 5 = the generic ADMM factorisation (kkt_invert: dpart_factor) on a problem of the dense fast path (factor_fast below)
   int dbg_flags;
   // TotalTime terms ON THE BLOCK CHAIN (tmx_problem_upload: the only reason for the dense engine are these terms and the QP is over
   // its size limit, or TMX_TOTAL_TIME_CHAIN=1): tt_chain = n_tt (<= TMX_TT_MAX) and qp_dense = 0 - the structured QP kernels carry
@@ -197,6 +198,11 @@ struct DevProblem
   // piecewise QP kernels factor the block-banded reduced KKT matrix with a DENSE first coupling (QpWs::Cd, rebuilt by kkt_factor) and
   // the diagonal far couplings po2 / po3 (band_factor, tmx_qp.h).  0 everywhere else.  (Last, in the padding behind eval_fast.)
   int band_pairs;
+  // factor_fast: the ADMM factorisation of the dense fast path with the interior inverses inside one wave (tmx_factor.h) can take the
+  // problem - the conditions of setup_fast, and the interior sub-matrices of a wave fit its 64 lanes (factor_fast_fits).  dbg_flags
+  // bit 5 selects the generic factorisation on such a problem, as bit 0 does with its scalar assembly (same bits;
+  // tests/test_fast_factor.py compares the two in one library).  (Last: the offsets of the fields above are what they were.)
+  int factor_fast;
 };
 TMX_HOSTDEVFN int slot_is_diff(int kind) { return kind == SLOT_JOINTVEL || kind == SLOT_JOINTVEL_INEQ; }
 #define TMX_TV_REC 5  // DevBatch::tv_aff record of one segment: cleaned Jacobian entries on x[t][j], x[t+1][j], tau[t+1] (upper row), constants of the upper / lower row

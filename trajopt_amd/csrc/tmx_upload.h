@@ -91,7 +91,7 @@ struct UploadHooks
 // Where the QP workspace lives and which thread carries which row (place_workspace).
 struct Placement
 {
-  int coef_far = 0, setup_fast = 0, polish_fast = 0, step_fast = 0, eval_fast = 0, tt_place = 0;  // DevProblem fields of the same names
+  int coef_far = 0, setup_fast = 0, polish_fast = 0, step_fast = 0, eval_fast = 0, factor_fast = 0, tt_place = 0;  // DevProblem fields of the same names
   int wave_ok = 0, wv_gmax = 2, wv_aux2 = 0;
   // tables to upload: DevProblem::row_perm (empty: slot order), wp_pst, row_epos, wv_plan (with wave_ok only)
   std::vector<int> row_perm, pst, epos, plan;

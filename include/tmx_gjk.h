@@ -10,7 +10,18 @@
  * primitive.  ONE statement of the arithmetic, included by the kernels and by the CPU oracle (bit-identical contact data on both
  * sides; fixed iteration caps, no recursion, no allocation).  tesseract / Bullet are absent third-party code: the contact data of
  * hull links are "parity unpinned" against them like the rest of the collision geometry - they are pinned
- * against brute-force geometry instead (tests/test_hull_geometry.py).
+ * against brute-force geometry instead (tests/test_hull_geometry.py: shapes in general position).
+ * The DEGENERATE contacts - parallel faces and edges, exact touching, gaps down to 1e-15, where the simplex of GJK is flat and the
+ * origin lies on the boundary of EPA's polytope - are pinned by tests/test_gjk_contact_edges.py against exact closed forms (mpmath).
+ * Five rules keep them right: a tetrahedron that is flat to round-off is never "inside" and offers all four faces
+ * (tmx_gjk_closest_tetra); EPA's start tetrahedron takes a point only if it leaves the simplex's plane by more than round-off; EPA's
+ * faces are turned outward by an interior point of the polytope, not by the origin (tmx_epa_make_face); the witnesses of a
+ * penetration come from a second GJK run on the sets pulled apart along the closest face's normal (end of tmx_gjk_epa), so that both
+ * are points of their sets; GJK's search direction on a triangle is the triangle's normal, not the weighted sum of its vertices
+ * (tmx_gjk_run: a link swept from a gap of 1e-9 into touching).
+ * What the interface cannot deliver: it returns two witnesses and no normal.  At exact touching, or a distance below one ulp of |pa|,
+ * pb rounds to pa and the caller's normal (tmx_contact_normal) falls back to (0, 0, 1) although EPA knew the face's normal: the
+ * distance is right, the direction of such a contact is arbitrary - on every build alike, so no parity test sees it.
  */
 #ifndef TMX_GJK_H_
 #define TMX_GJK_H_
@@ -191,7 +202,12 @@ TMX_GJK_FN int tmx_gjk_outside(const double* a, const double* b, const double* c
   const double so = -tmx_gjk_dot(n, a), sd = tmx_gjk_dot(n, ad);
   return so * sd <= 0.0;
 }
-/* returns 1 when the origin lies inside the tetrahedron (lam then untouched) */
+/* returns 1 when the origin lies inside the tetrahedron (lam then untouched).
+ * A tetrahedron that is FLAT to round-off (four support points of one facet of the Minkowski difference: parallel faces, the normal
+ * case of boxes on tables) has no inside, and the two numbers tmx_gjk_outside compares are then noise: six times its volume is
+ * measured against its largest face and longest edge, and below TMX_GJK_FLAT every face is a candidate - the four triangles cover the
+ * flat quadrilateral, the nearest of their closest points is its closest point. */
+#define TMX_GJK_FLAT 1e-12
 TMX_GJK_FN int tmx_gjk_closest_tetra(const double* w, double lam[4])
 {
   const double *a = w, *b = w + 3, *c = w + 6, *d = w + 9;
@@ -199,8 +215,27 @@ TMX_GJK_FN int tmx_gjk_closest_tetra(const double* w, double lam[4])
   int any = 0;
   const int F[4][4] = { { 0, 1, 2, 3 }, { 0, 2, 3, 1 }, { 0, 3, 1, 2 }, { 1, 3, 2, 0 } };
   const double* P[4] = { a, b, c, d };
+  int flat = 0;
+  {
+    double nn = 0.0, ll = 0.0, vol = 0.0;
+    for (int f = 0; f < 4; ++f)
+    {
+      const double *p0 = P[F[f][0]], *p1 = P[F[f][1]], *p2 = P[F[f][2]], *p3 = P[F[f][3]];
+      const double e1[3] = { p1[0] - p0[0], p1[1] - p0[1], p1[2] - p0[2] }, e2[3] = { p2[0] - p0[0], p2[1] - p0[1], p2[2] - p0[2] };
+      const double e3[3] = { p3[0] - p0[0], p3[1] - p0[1], p3[2] - p0[2] };
+      const double n[3] = { e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0] };
+      const double n2 = tmx_gjk_dot(n, n), l1 = tmx_gjk_dot(e1, e1), l2 = tmx_gjk_dot(e2, e2), l3 = tmx_gjk_dot(e3, e3);
+      nn = n2 > nn ? n2 : nn;
+      ll = l1 > ll ? l1 : ll;
+      ll = l2 > ll ? l2 : ll;
+      ll = l3 > ll ? l3 : ll;
+      if (f == 0)
+        vol = tmx_gjk_dot(n, e3);
+    }
+    flat = !(vol * vol > (TMX_GJK_FLAT * TMX_GJK_FLAT) * nn * ll);
+  }
   for (int f = 0; f < 4; ++f)
-    if (tmx_gjk_outside(P[F[f][0]], P[F[f][1]], P[F[f][2]], P[F[f][3]]))
+    if (flat || tmx_gjk_outside(P[F[f][0]], P[F[f][1]], P[F[f][2]], P[F[f][3]]))
     {
       double l3[3];
       tmx_gjk_closest_triangle(P[F[f][0]], P[F[f][1]], P[F[f][2]], l3);
@@ -237,7 +272,10 @@ typedef struct
   int alive;
 } tmx_epa_face;
 
-TMX_GJK_FN int tmx_epa_make_face(const double* W, int i, int j, int k, tmx_epa_face* f)
+/* A face of the polytope, its normal turned AWAY from the interior point c (the centroid of the start tetrahedron: it stays inside
+ * while the polytope grows).  dist = the signed distance of the face's plane from the origin: at a touching contact the origin lies ON
+ * the polytope's boundary, dist is round-off of either sign there, and the origin itself cannot say which side is outside. */
+TMX_GJK_FN int tmx_epa_make_face(const double* W, int i, int j, int k, const double* cin, tmx_epa_face* f)
 {
   const double *a = W + 3 * i, *b = W + 3 * j, *c = W + 3 * k;
   const double ab[3] = { b[0] - a[0], b[1] - a[1], b[2] - a[2] }, ac[3] = { c[0] - a[0], c[1] - a[1], c[2] - a[2] };
@@ -256,7 +294,8 @@ TMX_GJK_FN int tmx_epa_make_face(const double* W, int i, int j, int k, tmx_epa_f
   for (int r = 0; r < 3; ++r)
     f->n[r] = n[r] / len;
   f->dist = tmx_gjk_dot(f->n, a);
-  if (f->dist < 0.0) /* outward orientation (the origin is inside the polytope) */
+  const double ca[3] = { a[0] - cin[0], a[1] - cin[1], a[2] - cin[2] };
+  if (tmx_gjk_dot(f->n, ca) < 0.0) /* outward orientation */
   {
     f->v[1] = k;
     f->v[2] = j;
@@ -267,12 +306,13 @@ TMX_GJK_FN int tmx_epa_make_face(const double* W, int i, int j, int k, tmx_epa_f
   return 1;
 }
 
-/* Closest points (separated: returns 0, pa on A and pb on B at minimum distance) or penetration witnesses (overlapping: returns 1,
- * pa = the point of A deepest inside B, pb = the point of B's boundary it has to be moved to, |pa - pb| = the penetration depth). */
-TMX_GJK_FN int tmx_gjk_epa(const tmx_cvx* A, const tmx_cvx* B, double pa[3], double pb[3])
+/* GJK proper: the simplex of A - (B + sh) closest to the origin (W its vertices, SA / SB the points of A and of the UNMOVED B they come
+ * from, lam the weights of the closest point, *np their number).  Returns 1 when the origin lies on or in the simplex. */
+TMX_GJK_FN int tmx_gjk_run(const tmx_cvx* A, const tmx_cvx* B, const double sh[3], double* W, double* SA, double* SB, double lam[4], int* np)
 {
-  double W[4 * 3], SA[4 * 3], SB[4 * 3], lam[4] = { 1.0, 0.0, 0.0, 0.0 };
   int n = 0;
+  lam[0] = 1.0;
+  lam[1] = lam[2] = lam[3] = 0.0;
   double d[3] = { 1.0, 0.0, 0.0 }, v[3] = { 0.0, 0.0, 0.0 };
   {
     double sa[3], sb[3];
@@ -283,7 +323,7 @@ TMX_GJK_FN int tmx_gjk_epa(const tmx_cvx* A, const tmx_cvx* B, double pa[3], dou
     {
       SA[r] = sa[r];
       SB[r] = sb[r];
-      W[r] = sa[r] - sb[r];
+      W[r] = sa[r] - sb[r] - sh[r];
       v[r] = W[r];
     }
     n = 1;
@@ -308,7 +348,7 @@ TMX_GJK_FN int tmx_gjk_epa(const tmx_cvx* A, const tmx_cvx* B, double pa[3], dou
     tmx_cvx_support(A, nd, sa);
     tmx_cvx_support(B, v, sb);
     for (int r = 0; r < 3; ++r)
-      w[r] = sa[r] - sb[r];
+      w[r] = sa[r] - sb[r] - sh[r];
     /* no progress towards the origin: v is the closest point of the Minkowski difference */
     if (vv - tmx_gjk_dot(v, w) <= TMX_GJK_REL_TOL * vv)
       break;
@@ -357,7 +397,35 @@ TMX_GJK_FN int tmx_gjk_epa(const tmx_cvx* A, const tmx_cvx* B, double pa[3], dou
       for (int i = 0; i < n; ++i)
         v[r] += lam[i] * W[3 * i + r];
     }
+    /* The closest point of a TRIANGLE that is met in its interior: the weighted sum above carries the round-off of its O(size) terms
+     * in every component, so where |v| is 1e-9 of the size its DIRECTION is off by 1e-7 - more than the tilt between two nearly
+     * coplanar facets (a link swept from a gap of 1e-9 into touching), and the next support point and the stop test were decided by
+     * noise.  The triangle's normal has no such cancellation: v = N (W0 . N) / (N . N), exact in direction to round-off. */
+    if (n == 3)
+    {
+      const double e1[3] = { W[3] - W[0], W[4] - W[1], W[5] - W[2] }, e2[3] = { W[6] - W[0], W[7] - W[1], W[8] - W[2] };
+      const double N[3] = { e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0] };
+      const double nn = tmx_gjk_dot(N, N);
+      if (nn > 0.0)
+      {
+        const double c = tmx_gjk_dot(W, N) / nn;
+        for (int r = 0; r < 3; ++r)
+          v[r] = N[r] * c;
+      }
+    }
   }
+  *np = n;
+  return inside;
+}
+
+/* Closest points (separated: returns 0, pa on A and pb on B at minimum distance) or penetration witnesses (overlapping: returns 1,
+ * pa = the point of A deepest inside B, pb = the point of B's boundary it has to be moved to, |pa - pb| = the penetration depth). */
+TMX_GJK_FN int tmx_gjk_epa(const tmx_cvx* A, const tmx_cvx* B, double pa[3], double pb[3])
+{
+  double W[4 * 3], SA[4 * 3], SB[4 * 3], lam[4];
+  int n = 0;
+  const double sh0[3] = { 0.0, 0.0, 0.0 };
+  const int inside = tmx_gjk_run(A, B, sh0, W, SA, SB, lam, &n);
   if (!inside)
   {
     for (int r = 0; r < 3; ++r)
@@ -416,25 +484,32 @@ TMX_GJK_FN int tmx_gjk_epa(const tmx_cvx* A, const tmx_cvx* B, double pa[3], dou
     tmx_cvx_support(B, nd, sb);
     for (int r = 0; r < 3; ++r)
       w[r] = sa[r] - sb[r];
-    /* accept the point if it is affinely independent of the simplex */
-    double indep = 0.0;
+    /* accept the point if it is affinely independent of the simplex - measured against the sizes involved (the sine of the angle it
+     * makes with the simplex): the simplex of a touching contact lies IN a facet of the Minkowski difference, the support point along
+     * the facet's outward normal lies in it as well, and its distance from the simplex's plane is round-off, not zero */
+    double indep = 0.0, against = 0.0;
     if (nv == 1)
     {
       const double e[3] = { w[0] - EW[0], w[1] - EW[1], w[2] - EW[2] };
+      const double w2 = tmx_gjk_dot(w, w), e2 = tmx_gjk_dot(EW, EW);
       indep = tmx_gjk_dot(e, e);
+      against = w2 > e2 ? w2 : e2;
     }
     else if (nv == 2)
     {
       const double e[3] = { EW[3] - EW[0], EW[4] - EW[1], EW[5] - EW[2] }, f[3] = { w[0] - EW[0], w[1] - EW[1], w[2] - EW[2] };
       const double c[3] = { e[1] * f[2] - e[2] * f[1], e[2] * f[0] - e[0] * f[2], e[0] * f[1] - e[1] * f[0] };
       indep = tmx_gjk_dot(c, c);
+      against = tmx_gjk_dot(e, e) * tmx_gjk_dot(f, f);
     }
     else
     {
       const double f[3] = { w[0] - EW[0], w[1] - EW[1], w[2] - EW[2] };
-      indep = fabs(tmx_gjk_dot(dir, f));
+      const double h = tmx_gjk_dot(dir, f);
+      indep = h * h;
+      against = tmx_gjk_dot(dir, dir) * tmx_gjk_dot(f, f);
     }
-    if (indep > 1e-24)
+    if (indep > (TMX_GJK_FLAT * TMX_GJK_FLAT) * against)
     {
       for (int r = 0; r < 3; ++r)
       {
@@ -449,21 +524,23 @@ TMX_GJK_FN int tmx_gjk_epa(const tmx_cvx* A, const tmx_cvx* B, double pa[3], dou
     /* flat Minkowski difference (touching contact of lower-dimensional sets): zero depth at the simplex point nearest the origin */
     for (int r = 0; r < 3; ++r)
       pa[r] = pb[r] = 0.0;
-    const double l0 = 1.0 / (double)(n > 0 ? n : 1);
     for (int r = 0; r < 3; ++r)
       for (int i = 0; i < n; ++i)
       {
-        pa[r] += l0 * SA[3 * i + r];
-        pb[r] += l0 * SB[3 * i + r];
+        pa[r] += lam[i] * SA[3 * i + r];
+        pb[r] += lam[i] * SB[3 * i + r];
       }
     return 1;
   }
   tmx_epa_face F[TMX_EPA_MAX_FACE];
   int nf = 0;
-  tmx_epa_make_face(EW, 0, 1, 2, &F[nf++]);
-  tmx_epa_make_face(EW, 0, 3, 1, &F[nf++]);
-  tmx_epa_make_face(EW, 0, 2, 3, &F[nf++]);
-  tmx_epa_make_face(EW, 1, 3, 2, &F[nf++]);
+  double cin[3];
+  for (int r = 0; r < 3; ++r)
+    cin[r] = 0.25 * (EW[r] + EW[3 + r] + EW[6 + r] + EW[9 + r]);
+  tmx_epa_make_face(EW, 0, 1, 2, cin, &F[nf++]);
+  tmx_epa_make_face(EW, 0, 3, 1, cin, &F[nf++]);
+  tmx_epa_make_face(EW, 0, 2, 3, cin, &F[nf++]);
+  tmx_epa_make_face(EW, 1, 3, 2, cin, &F[nf++]);
   int bestf = 0;
   for (int it = 0; it < TMX_EPA_MAX_ITER; ++it)
   {
@@ -542,7 +619,7 @@ TMX_GJK_FN int tmx_gjk_epa(const tmx_cvx* A, const tmx_cvx* B, double pa[3], dou
         }
         slot = nf++;
       }
-      tmx_epa_make_face(EW, E[k][0], E[k][1], wi, &F[slot]);
+      tmx_epa_make_face(EW, E[k][0], E[k][1], wi, cin, &F[slot]);
     }
     if (full)
       break;
@@ -561,28 +638,54 @@ TMX_GJK_FN int tmx_gjk_epa(const tmx_cvx* A, const tmx_cvx* B, double pa[3], dou
   if (bestf < 0)
     bestf = 0;
   /* Witness points.  Depth and direction are those of the closest face (its plane supports the Minkowski difference: exact for
-   * polytopes).  The face is one TRIANGLE of a facet that may be a larger polygon, and the projection of the origin can fall outside
-   * the triangle (inside the facet): pa = the point of A the triangle's barycentric coordinates of the nearest triangle point give
-   * (a point of the contact region, as any narrow phase picks one for a face-face contact), pb = pa moved out of B along the
-   * normal - so |pa - pb| is the exact depth and pb - pa the exact direction. */
+   * polytopes).  The face is one TRIANGLE of a facet that may be a larger polygon, and the projection q of the origin can fall outside
+   * the triangle (inside the facet): the triangle alone cannot split q into a point of A minus a point of B.  So B is moved out of A
+   * along the normal by the depth plus a small gap eta (1e-6 of the polytope's size) and GJK finds the closest points of the now
+   * separated sets: pa = that point of A - a convex combination of A's vertices, whose partner on the unmoved B is pa - q to the
+   * round-off of GJK - and pb = pa - q, so |pa - pb| is the exact depth and pb - pa the exact direction.  (Should that run fail to
+   * separate them - it cannot, but for round-off - pa comes from the triangle's point nearest q as before.) */
   {
     const int i = F[bestf].v[0], j = F[bestf].v[1], k = F[bestf].v[2];
     const double q[3] = { F[bestf].n[0] * F[bestf].dist, F[bestf].n[1] * F[bestf].dist, F[bestf].n[2] * F[bestf].dist };
-    double ta[3], tb[3], tc[3], l3[3];
-    for (int r = 0; r < 3; ++r)
+    double size = 0.0;
+    for (int e = 0; e < nv; ++e)
     {
-      ta[r] = EW[3 * i + r] - q[r];
-      tb[r] = EW[3 * j + r] - q[r];
-      tc[r] = EW[3 * k + r] - q[r];
+      const double ww = tmx_gjk_dot(EW + 3 * e, EW + 3 * e);
+      size = ww > size ? ww : size;
     }
-    tmx_gjk_closest_triangle(ta, tb, tc, l3);
-    for (int r = 0; r < 3; ++r)
+    const double eta = 1e-6 * sqrt(size);
+    const double sh[3] = { F[bestf].n[0] * (F[bestf].dist + eta), F[bestf].n[1] * (F[bestf].dist + eta), F[bestf].n[2] * (F[bestf].dist + eta) };
+    int n2 = 0;
+    if (eta > 0.0 && !tmx_gjk_run(A, B, sh, W, SA, SB, lam, &n2))
     {
-      pa[r] = l3[0] * EA[3 * i + r] + l3[1] * EA[3 * j + r] + l3[2] * EA[3 * k + r];
-      pb[r] = pa[r] - q[r];
+      for (int r = 0; r < 3; ++r)
+      {
+        pa[r] = 0.0;
+        for (int e = 0; e < n2; ++e)
+          pa[r] += lam[e] * SA[3 * e + r];
+        pb[r] = pa[r] - q[r];
+      }
+    }
+    else
+    {
+      double ta[3], tb[3], tc[3], l3[3];
+      for (int r = 0; r < 3; ++r)
+      {
+        ta[r] = EW[3 * i + r] - q[r];
+        tb[r] = EW[3 * j + r] - q[r];
+        tc[r] = EW[3 * k + r] - q[r];
+      }
+      tmx_gjk_closest_triangle(ta, tb, tc, l3);
+      for (int r = 0; r < 3; ++r)
+      {
+        pa[r] = l3[0] * EA[3 * i + r] + l3[1] * EA[3 * j + r] + l3[2] * EA[3 * k + r];
+        pb[r] = pa[r] - q[r];
+      }
     }
   }
-  return 1;
+  /* a touching contact: the closest face passes through the origin to round-off.  Where that round-off is negative the sets are apart
+   * by it along the same normal - reported as such, so that pb - pa keeps the face's direction with the sign the caller expects */
+  return F[bestf].dist < 0.0 ? 0 : 1;
 }
 
 #endif /* TMX_GJK_H_ */

@@ -614,6 +614,50 @@ TMX_API tmx_status tmx_argmin_queries(tmx_ctx* ctx, int64_t* best_index /* Q, -1
 /* The winning trajectory of every query (the rule of tmx_argmin_queries, evaluated by this call): x_out[Q][T*D], gathered on the
  * device and copied once; the rows of queries without a converged seed are zero and found[q] (optional) = 0.  Local to the rank.  */
 TMX_API tmx_status tmx_best_trajectories(tmx_ctx* ctx, double* x_out /* Q x T x D */, int32_t* found /* Q, optional */);
+/* ---- Trajectory collision check: what the reference's tests and planners do with tesseract's checkTrajectory(contacts, manager,
+ *      state_solver, joint_names, traj, config) under a tesseract::collision::CollisionCheckConfig (trajopt/test/cast_cost_unit.cpp:
+ *      83-117: "in collision" before optimize(), "collision free" after it), on the uploaded robot and scene.  A collision TERM is a
+ *      penalty at its own resolution: a converged seed may still cut through an obstacle.  The check tests every contact (step t,
+ *      sub-state or swept sub-segment i, link primitive s, obstacle o) with the signed distance d the collision terms compute, at the
+ *      resolution of the config: types 0 / 1 at the waypoints; types 2..4 per segment (t, t+1) with cnt = 2 sub-states, or
+ *      ceil(dist / lvs) + 1 when the joint distance dist > lvs, clamped to max_substates (sub-state values as Eigen's LinSpaced) -
+ *      type 2 tests the cnt states, type 4 the cnt - 1 swept sub-segments, type 3 the one swept segment.  Unlike a term there is no
+ *      safety_margin_buffer, no fixed_steps filtering and no removeInvalidContactResults: the whole trajectory is tested.        */
+typedef struct
+{
+  int32_t evaluator_type;   /* as tmx_term::evaluator_type: 0 / 1 DISCRETE (at waypoints), 2 LVS_DISCRETE, 3 CONTINUOUS, 4 LVS_CONTINUOUS */
+  int32_t max_substates;    /* cap of sub-states per segment, types 2..4 (0 = 2, at most 0x7FFF): the rule of tmx_term::max_substates */
+  double margin;            /* a contact with distance < margin is a collision                                               */
+  double longest_valid_segment_length; /* types 2 and 4; type 3 never splits a segment                                        */
+} tmx_check_config;
+/* the closest contact of a trajectory (ties: the lowest (step, substate, primitive, obstacle)); all integers -1 and 1e300 without one */
+typedef struct
+{
+  double min_distance;
+  int32_t step, primitive, obstacle, substate;
+} tmx_check_worst;
+TMX_API void tmx_default_check_config(tmx_check_config* cfg); /* LVS_CONTINUOUS, margin 0, lvs 0.05, max_substates 32 */
+/* Checks n trajectories x_host[n][T][n_dof + use_time] (a time column is carried, not measured), or with x_host == NULL the current
+ * iterates of the batch (n must then equal the batch).  Per-step outputs [n][T], any of them optional: entry t is waypoint t for types
+ * 0 / 1 and segment (t, t+1) for types 2..4 (entry T-1 then holds 1e300 / 0); min_distance = the smallest d (1e300 when the scene has
+ * no link primitive or no obstacle), penetration = sum max(0, margin - d) over the contacts in ascending (i, s, o) order: what
+ * CollisionConstraint::violation returns for that step with coefficient 1.  A trajectory is free iff every min_distance >= margin.
+ * worst[n]: the closest contact of every trajectory.  Geometry only: both flavours, use_time problems, multi-query batches (the scene
+ * is shared).  TMX_ERR_STATE without an uploaded problem, with x_host == NULL without a batch, or while a launch is pending;
+ * TMX_ERR_INVALID for a null config, n < 1, non-finite x / margin / lvs, lvs <= 0 for types 2 / 4, a type outside 0..4, max_substates
+ * outside 0..0x7FFF; TMX_ERR_UNSUPPORTED for a cast type (3 / 4) on a problem whose link primitives still include capsules (the upload
+ * turns them into two-vertex hulls only when the description has a cast term: the swept volume of a capsule is not a capsule).  */
+TMX_API tmx_status tmx_check_trajectories(tmx_ctx* ctx, const tmx_check_config* cfg, const double* x_host, int32_t n,
+                                          double* min_distance /* n x T, optional */, double* penetration /* n x T, optional */,
+                                          tmx_check_worst* worst /* n, optional */);
+/* K7 per query over the COLLISION-FREE converged seeds: the rule of tmx_argmin_queries (lowest total_cost among OPT_CONVERGED seeds,
+ * ties: the lowest index; -1 and 1e300 when there is none) restricted to seeds whose trajectory is free under cfg.  Only converged
+ * seeds are checked; the per-seed clearance stays on the device, one reduction picks the winners and one copy returns them:
+ * best_min_distance[q] (optional) = the winner's smallest distance, x_out[q] (optional) its trajectory (zeros without a winner).
+ * Local to the rank; works with one query.  Errors as tmx_check_trajectories with x_host == NULL.                              */
+TMX_API tmx_status tmx_best_trajectories_checked(tmx_ctx* ctx, const tmx_check_config* cfg, int64_t* best_index /* Q */,
+                                                 double* best_cost /* Q */, double* best_min_distance /* Q, optional */,
+                                                 double* x_out /* Q x T x D, optional */);
 /* ... or let the library own its communicator: rank 0 calls tmx_nccl_unique_id and ships the 128 bytes to the other ranks by
  * any means (bench.py: torch.distributed broadcast); every rank then calls tmx_nccl_init (ncclCommInitRank on the context's
  * device and stream).  The communicator is destroyed with the context.                                           */

@@ -1445,6 +1445,26 @@ struct BasicTrustRegionSQPResults
   }
 };
 
+/** tesseract::collision::CollisionCheckConfig as far as a trajectory check reads it (mirror of tmx_check_config, include/tmx.h): the
+    evaluator type (0 / 1 DISCRETE at the waypoints, 2 LVS_DISCRETE, 3 CONTINUOUS, 4 LVS_CONTINUOUS), the contact margin, the longest valid
+    segment length of the LVS types and the cap of sub-states per segment.  Defaults: tmx_default_check_config. */
+struct CollisionCheckConfig
+{
+  int evaluator_type{ 4 };
+  int max_substates{ 32 };
+  double margin{ 0.0 };
+  double longest_valid_segment_length{ 0.05 };
+  tmx_check_config toTmx() const
+  {
+    tmx_check_config c;
+    c.evaluator_type = evaluator_type;
+    c.max_substates = max_substates;
+    c.margin = margin;
+    c.longest_valid_segment_length = longest_valid_segment_length;
+    return c;
+  }
+};
+
 /** Sibling of sco::BasicTrustRegionSQPMultiThreaded (optimizers.hpp:196-218): BasicTrustRegionSQP::optimize() for a batch
     of seeds on one MI355X.  Throws if no device is available — there is no CPU path behind it. */
 class BasicTrustRegionSQPBatchedHip
@@ -1523,6 +1543,7 @@ public:
       printAndThrow("must initialize before optimizing");
     const tmx_sqp_params p = param_.toTmx();
     check(tmx_problem_upload(ctx_, &prob_->desc(), &p, &osqp_));
+    uploaded_ = true;
     if (n_queries_ > 1)  // (before tmx_batch_set_x0: it runs the first exact evaluation)
     {
       check(tmx_queries_set(ctx_, n_queries_));
@@ -1620,6 +1641,75 @@ public:
     std::vector<bool> found;
   };
   const QueryBest& bestPerQuery() const { return query_best_; }
+
+  /** What tesseract's checkTrajectory tells the reference's tests and planners (trajopt/test/cast_cost_unit.cpp:83-117), from
+      tmx_check_trajectories: per trajectory and step (a waypoint for the discrete types, the segment (t, t+1) otherwise) the smallest
+      signed distance and the summed penetration below the margin, the closest contact, and whether the trajectory is free. */
+  struct TrajectoryCheck
+  {
+    std::vector<DblVec> min_distance, penetration;  // [n][n_steps]
+    std::vector<tmx_check_worst> worst;             // [n]
+    std::vector<bool> free;                         // every min_distance >= margin
+  };
+  /** Checks `trajs` (each in j_t_d order, like a seed) under cfg; an empty list checks the current iterates of the batch (after
+      optimize()).  With trajectories the problem is uploaded first when optimize() has not done so yet, so the initial trajectories can
+      be checked before optimize() as the reference's tests do. */
+  TrajectoryCheck checkTrajectories(const CollisionCheckConfig& cfg, const std::vector<DblVec>& trajs = {})
+  {
+    const std::size_t nv = numVars(), T = static_cast<std::size_t>(prob_->GetNumSteps());
+    const tmx_check_config c = cfg.toTmx();
+    std::vector<double> x;
+    for (const DblVec& t : trajs)
+    {
+      if (t.size() != nv)
+        printAndThrow("checkTrajectories: trajectory has wrong length. expected " + std::to_string(nv) + " got " + std::to_string(t.size()));
+      x.insert(x.end(), t.begin(), t.end());
+    }
+    if (!trajs.empty() && !uploaded_)
+    {
+      const tmx_sqp_params p = param_.toTmx();
+      check(tmx_problem_upload(ctx_, &prob_->desc(), &p, &osqp_));
+      uploaded_ = true;
+    }
+    const std::size_t n = trajs.empty() ? static_cast<std::size_t>(batch_) : trajs.size();
+    std::vector<double> md(n * T), pen(n * T);
+    TrajectoryCheck out;
+    out.worst.resize(n);
+    check(tmx_check_trajectories(ctx_, &c, trajs.empty() ? nullptr : x.data(), static_cast<int32_t>(n), md.data(), pen.data(), out.worst.data()));
+    for (std::size_t b = 0; b < n; ++b)
+    {
+      out.min_distance.emplace_back(md.begin() + static_cast<std::ptrdiff_t>(b * T), md.begin() + static_cast<std::ptrdiff_t>((b + 1) * T));
+      out.penetration.emplace_back(pen.begin() + static_cast<std::ptrdiff_t>(b * T), pen.begin() + static_cast<std::ptrdiff_t>((b + 1) * T));
+      bool fr = true;
+      for (double d : out.min_distance.back())
+        fr = fr && d >= cfg.margin;
+      out.free.push_back(fr);
+    }
+    return out;
+  }
+  /** the best COLLISION-FREE converged seed of every query under cfg after optimize() (tmx_best_trajectories_checked; works with one
+      query): QueryBest, and the winner's clearance (1e300: none) */
+  struct QueryBestChecked : QueryBest
+  {
+    DblVec min_distance;
+  };
+  QueryBestChecked bestPerQuery(const CollisionCheckConfig& cfg)
+  {
+    const std::size_t Q = static_cast<std::size_t>(n_queries_), nv = numVars();
+    const tmx_check_config c = cfg.toTmx();
+    QueryBestChecked out;
+    out.index.assign(Q, -1);
+    out.total_cost.assign(Q, 0.0);
+    out.min_distance.assign(Q, 0.0);
+    std::vector<double> qx(Q * nv);
+    check(tmx_best_trajectories_checked(ctx_, &c, out.index.data(), out.total_cost.data(), out.min_distance.data(), qx.data()));
+    for (std::size_t q = 0; q < Q; ++q)
+    {
+      out.x.emplace_back(qx.begin() + static_cast<std::ptrdiff_t>(q * nv), qx.begin() + static_cast<std::ptrdiff_t>((q + 1) * nv));
+      out.found.push_back(out.index[q] >= 0);
+    }
+    return out;
+  }
 
   DblVec& x() { return results_.x; }
   OptResults& results() { return results_; }
@@ -1745,6 +1835,7 @@ private:
   tmx_osqp_settings osqp_{};
   std::vector<double> seeds_;
   int32_t batch_{ 0 };
+  bool uploaded_{ false };  // tmx_problem_upload has run (optimize(), or checkTrajectories before it)
   OptResults results_;
   std::vector<OptResults> batch_results_;
   std::size_t best_{ 0 };

@@ -229,3 +229,31 @@ def default_osqp_settings():
     s.scaling, s.adaptive_rho, s.adaptive_rho_interval, s.max_iter = 10, 1, 50, 8192
     s.polishing, s.polish_refine_iter, s.check_termination, s.warm_starting = 1, 3, 25, 1
     return s
+
+
+class CheckConfig(C.Structure):
+    """tmx_check_config: the CollisionCheckConfig of a trajectory check (evaluator_type 0 / 1 DISCRETE at waypoints, 2 LVS_DISCRETE,
+    3 CONTINUOUS, 4 LVS_CONTINUOUS; a contact with distance < margin is a collision)"""
+    _fields_ = [
+        ("evaluator_type", C.c_int32), ("max_substates", C.c_int32),
+        ("margin", C.c_double), ("longest_valid_segment_length", C.c_double),
+    ]
+
+
+class CheckWorst(C.Structure):
+    """tmx_check_worst: the closest contact of a trajectory (all integers -1 without one)"""
+    _fields_ = [
+        ("min_distance", C.c_double),
+        ("step", C.c_int32), ("primitive", C.c_int32), ("obstacle", C.c_int32), ("substate", C.c_int32),
+    ]
+
+
+CHECK_WORST_DTYPE = [("min_distance", "<f8"), ("step", "<i4"), ("primitive", "<i4"), ("obstacle", "<i4"), ("substate", "<i4")]
+
+
+def default_check_config(evaluator_type: int = 4, margin: float = 0.0, longest_valid_segment_length: float = 0.05, max_substates: int = 32):
+    """tmx_default_check_config: LVS_CONTINUOUS, margin 0, longest valid segment 0.05, at most 32 sub-states per segment"""
+    c = CheckConfig()
+    c.evaluator_type, c.max_substates = evaluator_type, max_substates
+    c.margin, c.longest_valid_segment_length = margin, longest_valid_segment_length
+    return c

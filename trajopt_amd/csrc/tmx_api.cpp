@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "tmx_kernels.h"
+#include "tmx_check.h"
 #include "tmx_wave_kernels.h"
 #include "tmx_wave_plan.h"
 #include "tmx_row_perm.h"
@@ -3482,6 +3483,235 @@ tmx_status tmx_best_trajectories(tmx_ctx* ctx, double* x_out, int32_t* found)
   if (!ctx || !x_out)
     return TMX_ERR_INVALID;
   return argmin_queries(ctx, nullptr, nullptr, x_out, found);
+}
+
+void tmx_default_check_config(tmx_check_config* cfg)
+{
+  if (!cfg)
+    return;
+  cfg->evaluator_type = 4;  // LVS_CONTINUOUS
+  cfg->max_substates = 32;
+  cfg->margin = 0.0;
+  cfg->longest_valid_segment_length = 0.05;
+}
+
+// launch geometry and LDS of k_check_trajectories for n trajectories under cfg (validated here): the tile is the largest number of
+// items whose distance table and sub-state frames fit 64 KB of LDS (two workgroups and more per CU), at most the items of one step at
+// cnt = max_substates - the count depends on the data, so the worst case sizes the tables
+struct CheckPlan
+{
+  CheckArgs a;
+  size_t smem;
+  int nt;
+};
+static tmx_status check_plan(tmx_ctx* ctx, const tmx_check_config* cfg, int n, const char* who, CheckPlan& pl)
+{
+  const std::string w(who);
+  if (!cfg)
+  {
+    ctx->err = w + ": cfg == NULL (tmx_default_check_config fills one)";
+    return TMX_ERR_INVALID;
+  }
+  if (cfg->evaluator_type < 0 || cfg->evaluator_type > 4)
+  {
+    ctx->err = w + ": evaluator_type must be 0 .. 4 (0 / 1 DISCRETE, 2 LVS_DISCRETE, 3 CONTINUOUS, 4 LVS_CONTINUOUS)";
+    return TMX_ERR_INVALID;
+  }
+  if (cfg->max_substates < 0 || cfg->max_substates > 0x7FFF)
+  {
+    ctx->err = w + ": max_substates must be 0 .. 32767 (0 = 2)";
+    return TMX_ERR_INVALID;
+  }
+  if (!std::isfinite(cfg->margin) || !std::isfinite(cfg->longest_valid_segment_length))
+  {
+    ctx->err = w + ": non-finite margin or longest_valid_segment_length";
+    return TMX_ERR_INVALID;
+  }
+  const int type = cfg->evaluator_type;
+  if ((type == 2 || type == 4) && !(cfg->longest_valid_segment_length > 0.0))
+  {
+    ctx->err = w + ": longest_valid_segment_length must be > 0 for the LVS evaluators (types 2 and 4)";
+    return TMX_ERR_INVALID;
+  }
+  if (type >= 3 && ctx->hp.n_ls_capsule > 0)
+  {
+    ctx->err = w + ": a cast check (evaluator_type 3 / 4) of capsule links: the swept volume of a capsule is not a capsule, and the "
+                   "upload turns capsule links into two-vertex hulls only when the description has a cast collision term";
+    return TMX_ERR_UNSUPPORTED;
+  }
+  const int DK = ctx->hp.DK, T = ctx->hp.T;
+  const long long SO = (long long)ctx->hp.S * ctx->hp.O;
+  CheckArgs& a = pl.a;
+  a.type = type;
+  a.kmax = cfg->max_substates < 2 ? 2 : cfg->max_substates;
+  a.margin = cfg->margin;
+  a.lvs = cfg->longest_valid_segment_length;
+  a.converged_only = 0;
+  a.converged_code = ctx->hp.flavor == TMX_FLAVOR_SQP ? (int)TMX_SQP_CONVERGED : (int)TMX_OPT_CONVERGED;
+  pl.nt = ctx->nt_qp > 1 ? 256 : 1;  // (the host build runs a workgroup as one thread)
+  const long long nsub = type < 2 ? 1 : (type == 3 ? 1 : (type == 4 ? a.kmax - 1 : a.kmax));
+  const long long step_items = std::max<long long>(1, nsub * SO);  // items of one step, worst case
+  const long long so1 = std::max<long long>(1, SO);
+  auto fits = [&](long long tile) { return check_lds_doubles(DK, (int)tile, (int)(tile / so1 + 3), pl.nt) * sizeof(double) <= 64 * 1024; };
+  long long tile_max = (long long)((8192.0 - 2.0 * pl.nt - 2.0 - 36.0 * DK) / (12.0 * DK / (double)so1 + 1.0));
+  tile_max = std::max<long long>(1, tile_max);
+  while (tile_max > 1 && !fits(tile_max))
+    --tile_max;
+  long long tile = std::min(step_items, tile_max);
+  // default: about 2048 workgroups in the grid, whole steps per workgroup
+  long long chunks = std::max<long long>(1, std::min<long long>(T, (2048 + n - 1) / n));
+  long long spc = (T + chunks - 1) / chunks;
+  // TMX_CHECK_TILE=<items> (test hook, read at the call): a workgroup's LDS holds at most that many items - as many whole steps per
+  // chunk as fit (at least one), and a tile smaller than a step when one step does not fit
+  if (const char* e = std::getenv("TMX_CHECK_TILE"))
+  {
+    const long long want = std::max<long long>(1, std::atoll(e));
+    tile = std::min(tile, want);
+    spc = std::max<long long>(1, std::min<long long>(T, want / step_items));
+  }
+  chunks = (T + spc - 1) / spc;
+  a.tile = (int)tile;
+  a.fcap = (int)(tile / so1 + 3);
+  a.spc = (int)spc;
+  a.chunks = (int)chunks;
+  pl.smem = check_lds_doubles(DK, a.tile, a.fcap, pl.nt) * sizeof(double);
+  return TMX_OK;
+}
+static tmx_status check_launch(tmx_ctx* ctx, const CheckPlan& pl, const double* d_x, int n, double* d_min, double* d_pen, int* d_key)
+{
+  if (ctx->hull)
+    TMX_LAUNCH(k_check_trajectories_hull, n * pl.a.chunks, pl.nt, pl.smem, ctx->stream, ctx->dp, ctx->db, d_x, pl.a, d_min, d_pen, d_key);
+  else
+    TMX_LAUNCH(k_check_trajectories, n * pl.a.chunks, pl.nt, pl.smem, ctx->stream, ctx->dp, ctx->db, d_x, pl.a, d_min, d_pen, d_key);
+  HIPCHK(hipGetLastError());
+  return TMX_OK;
+}
+
+tmx_status tmx_check_trajectories(tmx_ctx* ctx, const tmx_check_config* cfg, const double* x_host, int32_t n, double* min_distance,
+                                  double* penetration, tmx_check_worst* worst)
+{
+  if (!ctx)
+    return TMX_ERR_INVALID;
+  if (!ctx->have_problem)
+  {
+    ctx->err = "tmx_check_trajectories: no problem uploaded (call tmx_problem_upload first)";
+    return TMX_ERR_STATE;
+  }
+  TMX_REFUSE_WHILE_PENDING(ctx);
+  if (n < 1)
+  {
+    ctx->err = "tmx_check_trajectories: n must be >= 1";
+    return TMX_ERR_INVALID;
+  }
+  CheckPlan pl;
+  tmx_status rc;
+  if ((rc = check_plan(ctx, cfg, n, "tmx_check_trajectories", pl)) != TMX_OK)
+    return rc;
+  const size_t T = (size_t)ctx->hp.T, NX = (size_t)ctx->hp.NX;
+  if (!x_host)
+  {
+    if (ctx->Bcap == 0)
+    {
+      ctx->err = "tmx_check_trajectories: x_host == NULL checks the current iterates, but the context holds no batch (call tmx_batch_set_x0 first)";
+      return TMX_ERR_STATE;
+    }
+    if (n != ctx->hb.B)
+    {
+      ctx->err = "tmx_check_trajectories: with x_host == NULL n must equal the batch (" + std::to_string(ctx->hb.B) + ")";
+      return TMX_ERR_INVALID;
+    }
+  }
+  else
+    for (size_t i = 0; i < (size_t)n * NX; ++i)
+      if (!std::isfinite(x_host[i]))
+      {
+        ctx->err = "tmx_check_trajectories: non-finite trajectory value";
+        return TMX_ERR_INVALID;
+      }
+  HIPCHK(hipSetDevice(ctx->device));
+  struct PoolGuard
+  {
+    std::vector<void*> pool;
+    ~PoolGuard() { free_pool(pool); }
+  } guard;
+  double *d_x = nullptr, *d_min = nullptr, *d_pen = nullptr;
+  int* d_key = nullptr;
+  tmx_check_worst* d_worst = nullptr;
+  if ((x_host && (rc = dalloc(ctx, guard.pool, &d_x, (size_t)n * NX, false)) != TMX_OK) ||
+      (rc = dalloc(ctx, guard.pool, &d_min, (size_t)n * T, false)) != TMX_OK || (rc = dalloc(ctx, guard.pool, &d_pen, (size_t)n * T, false)) != TMX_OK ||
+      (rc = dalloc(ctx, guard.pool, &d_key, (size_t)n * T * 3, false)) != TMX_OK ||
+      (worst && (rc = dalloc(ctx, guard.pool, &d_worst, (size_t)n, false)) != TMX_OK))
+    return rc;
+  if (x_host)
+    HIPCHK(hipMemcpyAsync(d_x, x_host, sizeof(double) * (size_t)n * NX, hipMemcpyHostToDevice, ctx->stream));
+  if ((rc = check_launch(ctx, pl, x_host ? d_x : ctx->hb.x, n, d_min, d_pen, d_key)) != TMX_OK)
+    return rc;
+  if (worst)
+  {
+    // the per-trajectory reduction over the per-step results (its own small launch: a trajectory may span several chunks)
+    TMX_LAUNCH(k_check_worst, (n + pl.nt - 1) / pl.nt, pl.nt, 0, ctx->stream, (int)n, (int)T, d_min, d_key, d_worst);
+    HIPCHK(hipGetLastError());
+  }
+  if ((rc = d2h(ctx, min_distance, d_min, (size_t)n * T)) != TMX_OK || (rc = d2h(ctx, penetration, d_pen, (size_t)n * T)) != TMX_OK ||
+      (rc = d2h(ctx, worst, d_worst, (size_t)n)) != TMX_OK)
+    return rc;
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return TMX_OK;
+}
+
+tmx_status tmx_best_trajectories_checked(tmx_ctx* ctx, const tmx_check_config* cfg, int64_t* best_index, double* best_cost,
+                                         double* best_min_distance, double* x_out)
+{
+  if (!ctx)
+    return TMX_ERR_INVALID;
+  if (!best_index || !best_cost)
+  {
+    ctx->err = "tmx_best_trajectories_checked: best_index and best_cost must not be NULL";
+    return TMX_ERR_INVALID;
+  }
+  if (!ctx->have_problem || ctx->Bcap == 0)
+  {
+    ctx->err = "tmx_best_trajectories_checked: the context holds no batch (tmx_problem_upload, tmx_batch_set_x0, run first)";
+    return TMX_ERR_STATE;
+  }
+  TMX_REFUSE_WHILE_PENDING(ctx);
+  const int B = ctx->hb.B, Q = ctx->n_queries, S = B / Q, NX = ctx->hp.NX, T = ctx->hp.T;
+  CheckPlan pl;
+  tmx_status rc;
+  if ((rc = check_plan(ctx, cfg, B, "tmx_best_trajectories_checked", pl)) != TMX_OK)
+    return rc;
+  pl.a.converged_only = 1;  // a workgroup of a seed that did not converge returns at once
+  HIPCHK(hipSetDevice(ctx->device));
+  struct PoolGuard
+  {
+    std::vector<void*> pool;
+    ~PoolGuard() { free_pool(pool); }
+  } guard;
+  double *d_min = nullptr, *d_pen = nullptr, *d_cost = nullptr, *d_clear = nullptr, *d_x = nullptr;
+  int* d_key = nullptr;
+  long long* d_idx = nullptr;
+  if ((rc = dalloc(ctx, guard.pool, &d_min, (size_t)B * T, false)) != TMX_OK || (rc = dalloc(ctx, guard.pool, &d_pen, (size_t)B * T, false)) != TMX_OK ||
+      (rc = dalloc(ctx, guard.pool, &d_key, (size_t)B * T * 3, false)) != TMX_OK || (rc = dalloc(ctx, guard.pool, &d_cost, (size_t)Q, false)) != TMX_OK ||
+      (rc = dalloc(ctx, guard.pool, &d_clear, (size_t)Q, false)) != TMX_OK || (rc = dalloc(ctx, guard.pool, &d_idx, (size_t)Q, false)) != TMX_OK ||
+      (x_out && (rc = dalloc(ctx, guard.pool, &d_x, (size_t)Q * NX, false)) != TMX_OK))
+    return rc;
+  // one check launch (the per-step minima of the converged seeds stay on the device), one reduction launch, one copy
+  if ((rc = check_launch(ctx, pl, ctx->hb.x, B, d_min, d_pen, d_key)) != TMX_OK)
+    return rc;
+  TMX_LAUNCH(k_argmin_queries_checked, Q, pl.nt, 16 * sizeof(double) + 18 * sizeof(int), ctx->stream, ctx->db, pl.a.converged_code, S, NX, T,
+             pl.a.margin, d_min, d_cost, d_idx, d_clear, d_x);
+  HIPCHK(hipGetLastError());
+  std::vector<long long> idx((size_t)Q);
+  HIPCHK(hipMemcpyAsync(idx.data(), d_idx, sizeof(long long) * (size_t)Q, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipMemcpyAsync(best_cost, d_cost, sizeof(double) * (size_t)Q, hipMemcpyDeviceToHost, ctx->stream));
+  if (best_min_distance)
+    HIPCHK(hipMemcpyAsync(best_min_distance, d_clear, sizeof(double) * (size_t)Q, hipMemcpyDeviceToHost, ctx->stream));
+  if (x_out)
+    HIPCHK(hipMemcpyAsync(x_out, d_x, sizeof(double) * (size_t)Q * NX, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  for (int q = 0; q < Q; ++q)
+    best_index[q] = idx[(size_t)q];
+  return TMX_OK;
 }
 
 tmx_status tmx_nccl_unique_id(uint8_t id[TMX_NCCL_UNIQUE_ID_BYTES])

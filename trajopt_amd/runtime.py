@@ -59,6 +59,9 @@ _SIGS = {
     "tmx_query_set_targets": ([C.c_void_p, C.c_int32, C.c_void_p, C.c_int32], C.c_int),
     "tmx_argmin_queries": ([C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
     "tmx_best_trajectories": ([C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+    "tmx_default_check_config": ([C.POINTER(abi.CheckConfig)], None),
+    "tmx_check_trajectories": ([C.c_void_p, C.POINTER(abi.CheckConfig), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+    "tmx_best_trajectories_checked": ([C.c_void_p, C.POINTER(abi.CheckConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
 }
 ABI_SYMBOLS = tuple(_SIGS.keys())
 
@@ -370,6 +373,41 @@ class Context:
         self._chk(self.lib.tmx_best_trajectories(self.h, _ptr(x), _ptr(found)))
         return x, found.astype(bool)
 
+    # ---- trajectory collision check ----
+    def default_check_config(self) -> abi.CheckConfig:
+        cfg = abi.CheckConfig()
+        self.lib.tmx_default_check_config(C.byref(cfg))
+        return cfg
+
+    def check_trajectories(self, cfg: abi.CheckConfig = None, x=None):
+        """tmx_check_trajectories under cfg (None: the library's default config) of the trajectories x[n][T][D], or of the current
+        iterates of the batch (x None): dict(min_distance [n][T], penetration [n][T], worst [n] (a structured array: min_distance, step,
+        primitive, obstacle, substate), free [n]: every min_distance >= margin).  Entry t is waypoint t for evaluator types 0 / 1 and
+        segment (t, t+1) for types 2..4"""
+        cfg = self.default_check_config() if cfg is None else cfg
+        if x is not None:
+            x = np.ascontiguousarray(x, dtype=np.float64)
+            if x.ndim == 2:
+                x = x[None]
+            if x.ndim != 3 or x.shape[1] != self.T or x.shape[2] != self.D:
+                raise TmxError(f"check_trajectories: x must be [n][{self.T}][{self.D}], got {list(x.shape)}")
+            n = x.shape[0]
+        else:
+            n = self.B
+        md, pen = np.zeros((n, self.T)), np.zeros((n, self.T))
+        worst = np.zeros(n, dtype=abi.CHECK_WORST_DTYPE)
+        self._chk(self.lib.tmx_check_trajectories(self.h, C.byref(cfg), _ptr(x), n, _ptr(md), _ptr(pen), _ptr(worst)))
+        return dict(min_distance=md, penetration=pen, worst=worst, free=(md >= cfg.margin).all(axis=1))
+
+    def best_trajectories_checked(self, cfg: abi.CheckConfig = None):
+        """tmx_best_trajectories_checked: the best COLLISION-FREE converged seed of every query under cfg: dict(index [Q] in the batch
+        (-1: none), total_cost [Q] (1e300: none), min_distance [Q] (the winner's clearance), x [Q][T][D] (zeros: none), found [Q])"""
+        cfg = self.default_check_config() if cfg is None else cfg
+        bi, bc, md = np.zeros(self.Q, np.int64), np.zeros(self.Q), np.zeros(self.Q)
+        x = np.zeros((self.Q, self.T, self.D))
+        self._chk(self.lib.tmx_best_trajectories_checked(self.h, C.byref(cfg), _ptr(bi), _ptr(bc), _ptr(md), _ptr(x)))
+        return dict(index=bi, total_cost=bc, min_distance=md, x=x, found=bi >= 0)
+
     def nccl_unique_id(self) -> bytes:
         buf = (C.c_uint8 * 128)()
         self._chk(self.lib.tmx_nccl_unique_id(buf))
@@ -480,8 +518,21 @@ class BatchedTrustRegionSQP:
         for cb in self._callbacks:
             cb(b, res)
 
-    def best_per_query(self):
-        """the best converged seed of every query: dict(index [Q] in the batch (-1: none converged), total_cost [Q], x [Q][T][D], found [Q])"""
+    def check_trajectories(self, cfg: abi.CheckConfig = None, x=None):
+        """Context.check_trajectories on the optimizer's problem: x [n][T][D] (e.g. the initial trajectories, as the reference's tests
+        check them before optimize()), or None for the current iterates of the batch.  Uploads the problem if that has not happened"""
+        if not self._uploaded:
+            self.desc = self.pci.to_desc()
+            self.ctx.upload(self.desc, self.params, self.osqp)
+            self._uploaded = True
+            self._queries_sent = False
+        return self.ctx.check_trajectories(cfg, x)
+
+    def best_per_query(self, check: abi.CheckConfig = None):
+        """the best converged seed of every query: dict(index [Q] in the batch (-1: none converged), total_cost [Q], x [Q][T][D], found [Q]);
+        with a CheckConfig the best COLLISION-FREE converged seed under it, and min_distance [Q] = its clearance"""
+        if check is not None:
+            return self.ctx.best_trajectories_checked(check)
         bi, bc = self.ctx.argmin_queries()
         x, found = self.ctx.best_trajectories()
         return dict(index=bi, total_cost=bc, x=x, found=found)

@@ -56,6 +56,9 @@ HipBatchedAdmmModel::HipBatchedAdmmModel(const ModelConfig::ConstPtr& config)
     settings_ = HipModelConfig(*osqp).settings;
   if (tmx_create(device, &ctx_) != TMX_OK)
     PRINT_AND_THROW("HipBatchedAdmmModel: no usable HIP device (there is no CPU fallback behind this model)");
+  // trajectory-sized models (more variables than the dense engine's limit) whose reduced KKT matrix is block tridiagonal under a
+  // reordering go to the block-tridiagonal engine; everything else stays on the dense one
+  (void)tmx_qp_engine_set(ctx_, TMX_QP_ENGINE_AUTO);
 }
 
 HipBatchedAdmmModel::~HipBatchedAdmmModel() { tmx_destroy(ctx_); }

@@ -24,6 +24,9 @@ HipQPSolver::HipQPSolver(int device)
   tmx_default_osqp_settings(&settings);  // warm start on, polish on, adaptive rho on, 8192 iterations, 1e-4 / 1e-6
   if (tmx_create(device, &ctx_) != TMX_OK)
     throw std::runtime_error("HipQPSolver: no usable HIP device (there is no CPU fallback behind this solver)");
+  // trajectory-sized QPs (more variables than the dense engine's limit) whose reduced KKT matrix is block tridiagonal under a
+  // reordering go to the block-tridiagonal engine; everything else stays on the dense one
+  (void)tmx_qp_engine_set(ctx_, TMX_QP_ENGINE_AUTO);
 }
 HipQPSolver::~HipQPSolver() { tmx_destroy(ctx_); }
 

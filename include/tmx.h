@@ -567,6 +567,28 @@ typedef struct
 TMX_API tmx_status tmx_qp_solve_batched(tmx_ctx* ctx, const tmx_qp_csc* qps, int32_t batch, const tmx_osqp_settings* settings,
                                         double* x, double* y, int32_t* cvx_status, tmx_qp_info* info, int32_t* active_flags);
 
+/* Engine of tmx_qp_solve_batched.  DENSE (the default): P and A expanded to dense matrices, an n x n Gauss-Jordan inverse per rho
+ * update - for QPs of a few dozen to a few hundred variables.  BLOCKS: the same OSQP algorithm on a block-tridiagonal factorisation
+ * of P + sigma I + A' diag(rho) A, whose blocks a reverse Cuthill-McKee ordering finds from the CSC arrays alone (trajectory QPs in
+ * the reference layout: variables of neighbouring waypoints coupled, penalty variables appended); a QP whose blocks exceed the
+ * engine's cap makes the call return TMX_ERR_UNSUPPORTED with the reason in tmx_last_error.  AUTO: per QP, BLOCKS when the QP has
+ * more variables than the dense engine's limit of the SQP path (448; TMX_DENSE_QP_MAX_N) and the chain is cheaper than the dense
+ * inverse by the flop model of DESIGN.md section 2.9, DENSE otherwise; a batch may mix engines.                                     */
+enum
+{
+  TMX_QP_ENGINE_DENSE = 0,
+  TMX_QP_ENGINE_AUTO = 1,
+  TMX_QP_ENGINE_BLOCKS = 2
+};
+/* A property of the context: it survives tmx_problem_upload.  TMX_ERR_INVALID for another value, TMX_ERR_STATE while a launch is
+ * pending.                                                                                                                        */
+TMX_API tmx_status tmx_qp_engine_set(tmx_ctx* ctx, int32_t engine);
+/* What the last tmx_qp_solve_batched used per QP (each array optional, `batch` entries; TMX_ERR_INVALID when batch differs from
+ * that call's): the engine (TMX_QP_ENGINE_DENSE / _BLOCKS), the block size and the number of blocks (0 / 0 on the dense engine),
+ * where the tiles of a factor step lived (0: dense engine, 1: LDS, 2: the HBM workspace).                                          */
+TMX_API tmx_status tmx_qp_engine_last(tmx_ctx* ctx, int32_t batch, int32_t* engine_out, int32_t* block_out, int32_t* n_blocks_out,
+                                      int32_t* placement_out);
+
 /* dual solution (OSQP solution->y, unscaled) of the last batched Model::optimize(): y_qp[problem * m_max + i], reference
  * row order; the reference reads it back for its explicit warm start (osqp_interface.cpp:346-348, 514-515)            */
 TMX_API tmx_status tmx_qp_duals(tmx_ctx* ctx, double* y_qp /* B * m_max */);

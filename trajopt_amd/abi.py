@@ -10,6 +10,7 @@ TMX_MAX_DOF = 16
 TMX_OK, TMX_ERR_INVALID, TMX_ERR_UNSUPPORTED, TMX_ERR_DEVICE, TMX_ERR_STATE, TMX_ERR_NCCL = range(6)
 (OPT_CONVERGED, OPT_SCO_ITERATION_LIMIT, OPT_PENALTY_ITERATION_LIMIT, OPT_TIME_LIMIT, OPT_FAILED, OPT_INVALID) = range(6)
 CVX_SOLVED, CVX_INFEASIBLE, CVX_FAILED = range(3)
+QP_ENGINE_DENSE, QP_ENGINE_AUTO, QP_ENGINE_BLOCKS = range(3)   # tmx_qp_engine_set
 FLAVOR_SCO, FLAVOR_SQP = 0, 1
 # trajopt_sqp::SQPStatus (types.h:216-225): the status values of FLAVOR_SQP problems
 (SQP_RUNNING, SQP_CONVERGED, SQP_ITERATION_LIMIT, SQP_PENALTY_ITERATION_LIMIT, SQP_TIME_LIMIT, SQP_QP_SOLVE_FAILED,

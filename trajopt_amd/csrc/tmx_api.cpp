@@ -14,6 +14,7 @@
 #include "tmx_wave_plan.h"
 #include "tmx_row_perm.h"
 #include "tmx_upload.h"
+#include "tmx_csc_order.h"
 
 #ifdef TMX_HOST_EMU
 #include <chrono>
@@ -96,6 +97,10 @@ struct tmx_ctx
   int n_dof{ 0 };
   // Bcap = 0 also says "no valid batch" (every entry point tests it): Balloc keeps the allocated capacity across an invalidation
   int Balloc{ 0 };
+  // tmx_qp_solve_batched: the engine selector (tmx_qp_engine_set; a property of the context: tmx_problem_upload leaves it) and what
+  // the last call used per QP (tmx_qp_engine_last)
+  int qp_engine{ TMX_QP_ENGINE_DENSE };
+  std::vector<int> qp_last_engine, qp_last_block, qp_last_nblocks, qp_last_place;
 };
 
 template <typename T>
@@ -2914,6 +2919,17 @@ tmx_status tmx_qp_solve_batched(tmx_ctx* ctx, const tmx_qp_csc* qps, int32_t bat
   std::vector<long long> Pp, Pi, Ap, Ai;
   std::vector<double> Px, Ax, q, l, u, xw, yw;
   long long ows = 0;
+  // block-tridiagonal engine (tmx_csc_blocks.h): the QPs it takes, their row-wise copies of P and A and their orderings
+  const int engine = ctx->qp_engine;
+  const int dense_limit = engine == TMX_QP_ENGINE_AUTO ? UploadHooks::read().dense_qp_max_n : 0;
+  std::vector<CbQp> cb;
+  std::vector<int> cPrp, cPrj, cPrk, cArp, cArj, cArk, cperm, cpos;
+  std::vector<int> last_engine((size_t)batch, TMX_QP_ENGINE_DENSE), last_block((size_t)batch, 0), last_nblocks((size_t)batch, 0), last_place((size_t)batch, 0);
+  const char* cb_min_env = std::getenv("TMX_CB_BLOCK_MIN");  // tuning hook: smallest block size of the partition (default TMX_CB_NB_MIN)
+  const int cb_min_block = cb_min_env ? std::max(1, std::atoi(cb_min_env)) : 0;
+  CscPartition part;
+  int part_of = -1;  // the QP `part` was computed for
+  size_t cb_smem = 0;
   for (int b = 0; b < batch; ++b)
   {
     const tmx_qp_csc& Q = qps[b];
@@ -2995,7 +3011,65 @@ tmx_status tmx_qp_solve_batched(tmx_ctx* ctx, const tmx_qp_csc* qps, int32_t bat
     gq.ov_m = (long long)l.size();
     gq.ows = ows;
     gq.warm = (Q.x_warm != nullptr && st.warm_starting) ? 1 : 0;
-    ows += (long long)((gen_ws_doubles(Q.n, Q.m) + 1) & ~(size_t)1);
+    bool blocks = false;
+    if (engine != TMX_QP_ENGINE_DENSE && !(engine == TMX_QP_ENGINE_AUTO && Q.n <= dense_limit))
+    {
+      // ordering and partition from the pattern arrays; skipped when they equal those of the QP before
+      bool same = part_of >= 0 && qps[part_of].n == Q.n && qps[part_of].m == Q.m;
+      if (same)
+      {
+        const tmx_qp_csc& R = qps[part_of];
+        same = std::equal(Q.P_p, Q.P_p + Q.n + 1, R.P_p) && std::equal(Q.A_p, Q.A_p + Q.n + 1, R.A_p) &&
+               std::equal(Q.P_i, Q.P_i + nzP, R.P_i) && std::equal(Q.A_i, Q.A_i + nzA, R.A_i);
+      }
+      if (!same)
+        part = csc_partition(Q.n, Q.m, Q.P_p, Q.P_i, Q.A_p, Q.A_i, cb_min_block);
+      part_of = b;
+      if (engine == TMX_QP_ENGINE_BLOCKS && !part.fits)
+      {
+        ctx->err = "tmx_qp_solve_batched: QP " + std::to_string(b) + " does not fit the block-tridiagonal engine: " + part.reason;
+        return TMX_ERR_UNSUPPORTED;
+      }
+      blocks = part.fits && (engine == TMX_QP_ENGINE_BLOCKS || part.profitable);
+    }
+    if (blocks)
+    {
+      CbQp c{};
+      c.n = Q.n;
+      c.m = Q.m;
+      c.nb = part.nb;
+      c.nblk = part.n_blocks;
+      c.place = part.placement;
+      c.warm = gq.warm;
+      c.slot = b;
+      c.oP = gq.oP;
+      c.oA = gq.oA;
+      c.oPp = gq.oPp;
+      c.oAp = gq.oAp;
+      c.ov_n = gq.ov_n;
+      c.ov_m = gq.ov_m;
+      c.ows = ows;
+      c.oPr = (long long)cPrj.size();
+      c.oPrp = (long long)cPrp.size();
+      c.oAr = (long long)cArj.size();
+      c.oArp = (long long)cArp.size();
+      c.operm = (long long)cperm.size();
+      ows += (long long)((cb_ws_doubles(Q.n, Q.m, part.nb, part.n_blocks, nzP, nzA) + 1) & ~(size_t)1);
+      csc_rows(Q.n, Q.n, Q.P_p, Q.P_i, /*skip_diagonal=*/true, cPrp, cPrj, cPrk);
+      csc_rows(Q.m, Q.n, Q.A_p, Q.A_i, /*skip_diagonal=*/false, cArp, cArj, cArk);
+      cperm.insert(cperm.end(), part.perm.begin(), part.perm.end());
+      cpos.insert(cpos.end(), part.pos.begin(), part.pos.end());
+      cb.push_back(c);
+      last_engine[(size_t)b] = TMX_QP_ENGINE_BLOCKS;
+      last_block[(size_t)b] = part.nb;
+      last_nblocks[(size_t)b] = part.n_blocks;
+      last_place[(size_t)b] = part.placement;
+      // LDS: the fixed part, then the two tiles of a factor step (placement 1) or, in the same place, the partial sums of a sweep step
+      cb_smem = std::max(cb_smem, (size_t)TMX_CB_LDS_FIXED + std::max(part.placement == TMX_CB_PLACE_LDS ? 2 * (size_t)part.nb * part.nb : (size_t)0,
+                                                                       2 * (size_t)TMX_CB_PARTS * part.nb));
+    }
+    else
+      ows += (long long)((gen_ws_doubles(Q.n, Q.m) + 1) & ~(size_t)1);
     Pp.insert(Pp.end(), Q.P_p, Q.P_p + Q.n + 1);
     Ap.insert(Ap.end(), Q.A_p, Q.A_p + Q.n + 1);
     Pi.insert(Pi.end(), Q.P_i, Q.P_i + nzP);
@@ -3062,17 +3136,116 @@ tmx_status tmx_qp_solve_batched(tmx_ctx* ctx, const tmx_qp_csc* qps, int32_t bat
   D.xw = dxw;
   D.yw = dyw;
   D.flags_out = d_flags;
-  TMX_LAUNCH(k_qp_generic, batch, ctx->nt_qp > 1 ? 256 : 1, 320 * sizeof(double), ctx->stream, d_g, D, st);
-  hipError_t e = hipStreamSynchronize(ctx->stream);
+  std::vector<tmx_qp_info> hinfo((size_t)batch);
+  std::vector<int> dslot;  // mixed batch: the caller's index of every QP of the dense launch, and that launch's info records
+  tmx_qp_info* d_dinfo = nullptr;
+  hipError_t e = hipSuccess;
+#if TMX_CB_PROF
+  int cb_prof_slots = 0;
+  long long* cb_prof_dev = nullptr;
+#endif
+  if (cb.empty())
+    TMX_LAUNCH(k_qp_generic, batch, ctx->nt_qp > 1 ? 256 : 1, 320 * sizeof(double), ctx->stream, d_g, D, st);
+  else
+  {
+    // one launch per engine.  Both kernels write x, y and the flags at the QP's own offsets of the caller's order; the dense
+    // kernel indexes its info records by workgroup, so its QPs get a compact list and their records are scattered below.
+    std::vector<GenQp> gd;
+    for (int b = 0; b < batch; ++b)
+      if (last_engine[(size_t)b] == TMX_QP_ENGINE_DENSE)
+      {
+        gd.push_back(g[(size_t)b]);
+        dslot.push_back(b);
+      }
+    CbData C{};
+    CbQp* d_cb = nullptr;
+    GenQp* d_gd = nullptr;
+    int *dPrp = nullptr, *dPrj = nullptr, *dPrk = nullptr, *dArp = nullptr, *dArj = nullptr, *dArk = nullptr, *dperm = nullptr, *dpos = nullptr;
+    up(&d_cb, cb);
+    up(&dPrp, cPrp);
+    up(&dPrj, cPrj);
+    up(&dPrk, cPrk);
+    up(&dArp, cArp);
+    up(&dArj, cArj);
+    up(&dArk, cArk);
+    up(&dperm, cperm);
+    up(&dpos, cpos);
+    if (!gd.empty())
+    {
+      up(&d_gd, gd);
+      if (rc == TMX_OK)
+        rc = dalloc(ctx, pool, &d_dinfo, gd.size());
+    }
+    if (rc != TMX_OK)
+    {
+      free_pool(pool);
+      return rc;
+    }
+    C.g = D;
+    C.Prp = dPrp;
+    C.Prj = dPrj;
+    C.Prk = dPrk;
+    C.Arp = dArp;
+    C.Arj = dArj;
+    C.Ark = dArk;
+    C.perm = dperm;
+    C.pos = dpos;
+#if TMX_CB_PROF
+    if ((rc = dalloc(ctx, pool, &C.prof, (size_t)batch * 8)) != TMX_OK)
+    {
+      free_pool(pool);
+      return rc;
+    }
+    long long* const d_prof = C.prof;
+    cb_prof_slots = batch;
+    cb_prof_dev = d_prof;
+#endif
+#ifndef TMX_HOST_EMU
+    if (cb_smem * sizeof(double) > 48 * 1024)
+      e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_qp_csc_blocks), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              static_cast<int>(cb_smem * sizeof(double)));
+#endif
+    if (e == hipSuccess)
+      TMX_LAUNCH(k_qp_csc_blocks, (int)cb.size(), ctx->nt_qp > 1 ? 256 : 1, cb_smem * sizeof(double), ctx->stream, d_cb, C, st);
+    if (e == hipSuccess && !gd.empty())
+    {
+      GenData Dd = D;
+      Dd.info = d_dinfo;
+      TMX_LAUNCH(k_qp_generic, (int)gd.size(), ctx->nt_qp > 1 ? 256 : 1, 320 * sizeof(double), ctx->stream, d_gd, Dd, st);
+    }
+  }
+  if (e == hipSuccess)
+    e = hipStreamSynchronize(ctx->stream);
   if (e == hipSuccess)
     e = hipGetLastError();
-  std::vector<tmx_qp_info> hinfo((size_t)batch);
   if (e == hipSuccess)
     e = hipMemcpy(x, D.x_out, sizeof(double) * q.size(), hipMemcpyDeviceToHost);
   if (e == hipSuccess && !l.empty())
     e = hipMemcpy(y, D.y_out, sizeof(double) * l.size(), hipMemcpyDeviceToHost);
   if (e == hipSuccess)
     e = hipMemcpy(hinfo.data(), D.info, sizeof(tmx_qp_info) * batch, hipMemcpyDeviceToHost);
+#if TMX_CB_PROF
+  if (e == hipSuccess && cb_prof_dev)
+  {
+    // profiling build: ticks of 10 ns per QP of the block-tridiagonal engine, to stderr
+    std::vector<long long> hp((size_t)cb_prof_slots * 8);
+    e = hipMemcpy(hp.data(), cb_prof_dev, sizeof(long long) * hp.size(), hipMemcpyDeviceToHost);
+    for (int b = 0; b < cb_prof_slots; ++b)
+      if (last_engine[(size_t)b] == TMX_QP_ENGINE_BLOCKS)
+      {
+        const long long* t = &hp[(size_t)b * 8];
+        std::fprintf(stderr, "cb_prof qp %d admm_assembly %lld admm_factor %lld admm_sweeps %lld polish_total %lld polish_assembly %lld polish_factor %lld polish_sweeps %lld total %lld\n",
+                     b, t[0], t[1], t[2], t[3], t[4], t[5], t[6], t[7]);
+      }
+  }
+#endif
+  if (e == hipSuccess && !dslot.empty())
+  {
+    std::vector<tmx_qp_info> dinfo(dslot.size());
+    e = hipMemcpy(dinfo.data(), d_dinfo, sizeof(tmx_qp_info) * dslot.size(), hipMemcpyDeviceToHost);
+    for (size_t k = 0; k < dslot.size(); ++k)
+      hinfo[(size_t)dslot[k]] = dinfo[k];
+  }
   if (e == hipSuccess && active_flags && !l.empty())
     e = hipMemcpy(active_flags, d_flags, sizeof(int) * l.size(), hipMemcpyDeviceToHost);
   free_pool(pool);
@@ -3081,6 +3254,10 @@ tmx_status tmx_qp_solve_batched(tmx_ctx* ctx, const tmx_qp_csc* qps, int32_t bat
     ctx->err = std::string("tmx_qp_solve_batched: ") + hipGetErrorString(e);
     return TMX_ERR_DEVICE;
   }
+  ctx->qp_last_engine = last_engine;
+  ctx->qp_last_block = last_block;
+  ctx->qp_last_nblocks = last_nblocks;
+  ctx->qp_last_place = last_place;
   for (int b = 0; b < batch; ++b)
   {
     const int s = hinfo[(size_t)b].osqp_status;
@@ -3088,6 +3265,44 @@ tmx_status tmx_qp_solve_batched(tmx_ctx* ctx, const tmx_qp_csc* qps, int32_t bat
       info[b] = hinfo[(size_t)b];
     if (cvx_status)  // OSQPModel::optimize, osqp_interface.cpp:565-614
       cvx_status[b] = (s == 1 || s == 2) ? TMX_CVX_SOLVED : ((s == 3 || s == 4 || s == 5 || s == 6) ? TMX_CVX_INFEASIBLE : TMX_CVX_FAILED);
+  }
+  return TMX_OK;
+}
+
+tmx_status tmx_qp_engine_set(tmx_ctx* ctx, int32_t engine)
+{
+  if (!ctx)
+    return TMX_ERR_INVALID;
+  TMX_REFUSE_WHILE_PENDING(ctx);
+  if (engine != TMX_QP_ENGINE_DENSE && engine != TMX_QP_ENGINE_AUTO && engine != TMX_QP_ENGINE_BLOCKS)
+  {
+    ctx->err = "tmx_qp_engine_set: engine must be TMX_QP_ENGINE_DENSE, _AUTO or _BLOCKS";
+    return TMX_ERR_INVALID;
+  }
+  ctx->qp_engine = engine;
+  return TMX_OK;
+}
+
+tmx_status tmx_qp_engine_last(tmx_ctx* ctx, int32_t batch, int32_t* engine_out, int32_t* block_out, int32_t* n_blocks_out, int32_t* placement_out)
+{
+  if (!ctx)
+    return TMX_ERR_INVALID;
+  TMX_REFUSE_WHILE_PENDING(ctx);
+  if (batch < 1 || (size_t)batch != ctx->qp_last_engine.size())
+  {
+    ctx->err = "tmx_qp_engine_last: batch differs from the last tmx_qp_solve_batched (" + std::to_string(ctx->qp_last_engine.size()) + " QPs)";
+    return TMX_ERR_INVALID;
+  }
+  for (int b = 0; b < batch; ++b)
+  {
+    if (engine_out)
+      engine_out[b] = ctx->qp_last_engine[(size_t)b];
+    if (block_out)
+      block_out[b] = ctx->qp_last_block[(size_t)b];
+    if (n_blocks_out)
+      n_blocks_out[b] = ctx->qp_last_nblocks[(size_t)b];
+    if (placement_out)
+      placement_out[b] = ctx->qp_last_place[(size_t)b];
   }
   return TMX_OK;
 }

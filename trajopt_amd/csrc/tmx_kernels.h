@@ -4,6 +4,7 @@
 #include "tmx_solve.h"
 #include "tmx_step.h"
 #include "tmx_generic.h"
+#include "tmx_csc_blocks.h"
 
 // scratch of the term / structure kernels: dynamic LDS, or this workgroup's slice of Bt->ws_hbm for long-horizon
 // problems whose scratch exceeds the LDS (the LDS-resident QP kernels never take this branch: they use smem directly)

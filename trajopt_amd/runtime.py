@@ -42,6 +42,8 @@ _SIGS = {
     "tmx_qp_solve": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
     "tmx_qp_solve_batched": ([C.c_void_p, C.POINTER(abi.QpCsc), C.c_int32, C.POINTER(abi.OsqpSettings), C.c_void_p, C.c_void_p,
                               C.c_void_p, C.POINTER(abi.QpInfo), C.c_void_p], C.c_int),
+    "tmx_qp_engine_set": ([C.c_void_p, C.c_int32], C.c_int),
+    "tmx_qp_engine_last": ([C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
     "tmx_qp_active_set": ([C.c_void_p, C.c_void_p], C.c_int),
     "tmx_qp_duals": ([C.c_void_p, C.c_void_p], C.c_int),
     "tmx_argmin": ([C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_double)], C.c_int),
@@ -321,6 +323,17 @@ class Context:
             on += ns[b]
             om += ms[b]
         return out
+
+    def qp_engine_set(self, engine: int):
+        """tmx_qp_engine_set: the engine of the following qp_solve_batched calls (abi.QP_ENGINE_DENSE / _AUTO / _BLOCKS)"""
+        self._chk(self.lib.tmx_qp_engine_set(self.h, int(engine)))
+
+    def qp_engine_last(self, batch: int):
+        """tmx_qp_engine_last: per QP of the last qp_solve_batched the engine, the block size, the number of blocks and the
+        placement of the factor tiles (0: dense engine, 1: LDS, 2: HBM workspace), as int32 arrays"""
+        out = [np.zeros(batch, np.int32) for _ in range(4)]
+        self._chk(self.lib.tmx_qp_engine_last(self.h, int(batch), *[_ptr(a) for a in out]))
+        return dict(engine=out[0], block=out[1], n_blocks=out[2], placement=out[3])
 
     def qp_duals(self):
         """dual solution of the last qp_solve() / SQP step, reference row order: [B][m_max]"""

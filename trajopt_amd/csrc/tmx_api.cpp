@@ -4066,7 +4066,7 @@ __attribute__((visibility("default"))) tmx_status tmx_debug_admm_iters(tmx_ctx* 
 // diagonal KKT blocks instead of the MFMA one, bit 1 = generic QP setup, bit 2 = generic polish on the dense fast path, bit 3 = generic
 // SQP shell around the QP solve (qp_structure) on a problem the specialised one can take, bit 4 = the hashes of P by the loop over its
 // columns and the generic exact evaluation and model values on a problem of eval_fast, bit 5 = the generic ADMM factorisation on a
-// problem of factor_fast
+// problem of factor_fast, bit 6 = one elimination step per barrier in the separator inverse of factor_fast
 __attribute__((visibility("default"))) tmx_status tmx_debug_set_flags(tmx_ctx* ctx, int flags)
 {
   if (!ctx || !ctx->have_problem || !ctx->dp)

@@ -14,8 +14,9 @@
 //  * every entry of G sees gj_rows' operations on gj_rows' operands: fma(nmp, M[k][c], M[i][c]) with nmp = i == k ? piv - 1 : -m_ik piv,
 //    m_ik from row k by the sign rule, the pivot column overwritten by piv / nmp, piv = fast_rcp of the updated M[k+1][k+1]; only the
 //    thread that holds a row and the kind of barrier differ
-//  * the cached weights are admm_cache_weights' expressions; the assembly of the diagonal blocks and the separator inverse are the
-//    generic functions, called
+//  * the cached weights are admm_cache_weights' expressions; the assembly of the diagonal blocks is the generic function, called
+//  * the separator inverse pays its workgroup barrier once per three elimination steps (gj_sep_rows below; bit 6 of dbg_flags keeps
+//    gj_rows, tests/test_factor_lookahead.py compares the three)
 #pragma once
 #include "tmx_qp.h"
 
@@ -174,6 +175,189 @@ TMX_DEVFN void gj_wave_rows(tmx_lds_d* G, tmx_lds_d* buf, const tmx_lds_d* S, co
   }
 }
 
+// The separator inverse (gj_rows<W, true> on one matrix: lane = row, wave = column quarter of the row stride Zst) with ONE workgroup
+// barrier and one LDS round trip per group of LA elimination steps.  The owners of rows k0 .. k0 + LA - 1 publish them as they stand
+// before step k0, with the reciprocal of the pivot of step k0.  Every lane then carries PRIVATE copies of the published rows through
+// the group: before it applies step k0 + s to its own row it advances the copies of the rows behind by that step - for row t > s the
+// multiplier nm = -r_s[k0 + t] piv_s, fma(nm, r_s[c], r_t[c]) on the entries it needs (its own column segment, entry i, the entries
+// k0 + u of the rows still to come), nm itself in the pivot column - and takes piv_t = fast_rcp(r_t[k0 + t]).  These are the IEEE
+// operations of the owner of row t on the owner's operands, so a copy holds the bits the owner would have published, and every entry of
+// the matrix still sees gj_rows' operations on gj_rows' operands.  The multipliers depend on 2 LA + LA (LA - 1) / 2 scalars only: they
+// come first, the row FMAs follow with known multipliers.  The entry of the next group's first pivot and its reciprocal are formed in
+// front of the row FMAs by every lane of the wave that holds its column (gj_wave_rows does the same with `rc`).
+// buf: 2 LA (Zst + 2) doubles, two parities of LA row buffers of [row, pivot reciprocal, pad] (gj_sep_buf_doubles).
+// NS steps of one group, NS <= LA (the last group may be short); kn = k0 + NS < ns: there is a next group to publish for
+template <int W, int NS, int LA>
+TMX_DEVFN void gj_sep_group(double (&val)[W], const tmx_lds_d* rin, tmx_lds_d* rout, int Zst, int wn, int j0, int i, int k0, bool more)
+{
+  const int bs = Zst + 2;
+  const int kk0 = TMX_UNI_I(k0 - j0);  // position of the group's first pivot column in this wave's segment
+  const int kkn = kk0 + NS;       // ... and of the next group's
+  const int kcn = TMX_UNI_I(kkn < 0 ? 0 : (kkn >= W ? W - 1 : kkn));
+  double piv[NS], ri[NS], rx[NS][NS], nmp[NS], pcv[NS], nm[NS][NS], e[NS];
+  tmx_d2 rs[NS][W / 2];
+  piv[0] = rin[Zst];
+#pragma unroll
+  for (int s = 0; s < NS; ++s)
+  {
+    ri[s] = rin[s * bs + i];
+    e[s] = rin[s * bs + k0 + NS];  // (column k0 + NS <= ns < Zst)
+#pragma unroll
+    for (int u = s + (s ? 0 : 1); u < NS; ++u)
+      rx[s][u] = rin[s * bs + k0 + u];
+  }
+#pragma unroll
+  for (int s = 0; s < NS; ++s)
+#pragma unroll
+    for (int c = 0; c < W / 2; ++c)
+      rs[s][c] = *((const tmx_lds_d2*)(rin + s * bs + j0) + c);
+  // the multipliers of the group: step k0 + s on the own row (nmp, pcv) and on the copies of the rows behind (nm[t][s])
+#pragma unroll
+  for (int s = 0; s < NS; ++s)
+  {
+    const int k = k0 + s;
+    if (s > 0)
+      piv[s] = fast_rcp(rx[s][s]);
+    const double mik = (i < k) ? -ri[s] : ri[s];  // column k from row k by (anti)symmetry
+    const bool prow = i == k;
+    double nmp_row = piv[s] - 1.0, nmp_else = -mik * piv[s];
+    nmp[s] = prow ? nmp_row : nmp_else;
+    pcv[s] = prow ? piv[s] : nmp[s];  // value of the entry in the pivot column
+#pragma unroll
+    for (int t = s + 1; t < NS; ++t)
+    {
+      nm[t][s] = -rx[s][t] * piv[s];  // (row t > k: its column k is r_s[k0 + t] itself)
+#pragma unroll
+      for (int u = t; u < NS; ++u)
+        rx[t][u] = __builtin_fma(nm[t][s], rx[s][u], rx[t][u]);
+      const double adv = __builtin_fma(nm[t][s], ri[s], ri[t]);
+      ri[t] = prow ? nm[t][s] : adv;  // (entry i is the pivot column on the lane of row k)
+    }
+  }
+  // the next group's first pivot M[kn][kn] after the NS steps and its reciprocal, in front of the row FMAs
+  const bool pw = more && kkn >= 0 && kkn < wn;  // (wave-uniform)
+  double rcn = 0.0;
+  if (pw)
+  {
+    double vn = val[kcn];
+#pragma unroll
+    for (int s = 0; s < NS; ++s)
+    {
+#pragma unroll
+      for (int t = s + 1; t < NS; ++t)
+        e[t] = __builtin_fma(nm[t][s], e[s], e[t]);
+      vn = __builtin_fma(nmp[s], e[s], vn);
+    }
+    rcn = fast_rcp(vn);
+    pin(rcn);
+  }
+  // the rows: step k0 + s on the copies of the rows behind, then on the own row
+#pragma unroll
+  for (int s = 0; s < NS; ++s)
+  {
+    const int kk = kk0 + s;
+    // (the index is clamped before use and handed back as a scalar: gj_rows, round 6)
+    const int kc = TMX_UNI_I(kk < 0 ? 0 : (kk >= W ? W - 1 : kk));
+    const bool kin = kk >= 0 && kk < wn;
+#pragma unroll
+    for (int t = s + 1; t < NS; ++t)
+    {
+      double rt[W];
+#pragma unroll
+      for (int c = 0; c < W / 2; ++c)
+      {
+        rt[2 * c] = __builtin_fma(nm[t][s], rs[s][c].x, rs[t][c].x);
+        rt[2 * c + 1] = __builtin_fma(nm[t][s], rs[s][c].y, rs[t][c].y);
+      }
+      const double keep = rt[kc];
+      rt[kc] = kin ? nm[t][s] : keep;
+#pragma unroll
+      for (int c = 0; c < W / 2; ++c)
+        rs[t][c] = tmx_d2{ rt[2 * c], rt[2 * c + 1] };
+    }
+#pragma unroll
+    for (int c = 0; c < W / 2; ++c)
+    {
+      val[2 * c] = __builtin_fma(nmp[s], rs[s][c].x, val[2 * c]);
+      val[2 * c + 1] = __builtin_fma(nmp[s], rs[s][c].y, val[2 * c + 1]);
+    }
+    const double keep = val[kc];
+    val[kc] = kin ? pcv[s] : keep;
+  }
+  // the owners of the next group's rows publish them into the other parity
+  const int kn = k0 + NS;
+  if (i >= kn && i < kn + LA)
+  {
+    tmx_lds_d* rb = rout + (i - kn) * bs;
+#pragma unroll
+    for (int c = 0; c < W; c += 2)
+      if (c < wn)
+        *(tmx_lds_d2*)(rb + j0 + c) = tmx_d2{ val[c], val[c + 1] };
+    if (pw && i == kn)
+      rb[Zst] = rcn;
+  }
+}
+TMX_HOSTDEVFN int gj_sep_buf_doubles(int Zst, int LA) { return 2 * LA * (Zst + 2); }
+template <int W, int LA>
+TMX_DEVFN void gj_sep_rows(tmx_lds_d* M, tmx_lds_d* buf, int Zst, int ns, int tid)
+{
+  static_assert(LA >= 1 && LA <= 3, "group size");
+  const int wn = Zst >> 2, j0 = TMX_UNI_I(((tid >> 6) & 3) * wn);
+  const bool active = (tid & 63) < ns && tid < 256;
+  const int i = active ? (tid & 63) : 0;
+  const int bs = Zst + 2;
+  tmx_lds_d* Mr = M + i * Zst + j0;
+  // (all W register slots are loaded and updated, slots >= wn hold what follows the segment and are never stored: gj_rows)
+  double val[W];
+#pragma unroll
+  for (int c = 0; c < W; c += 2)
+  {
+    const tmx_d2 t = *(const tmx_lds_d2*)(Mr + c);
+    val[c] = active ? t.x : 0.0;
+    val[c + 1] = active ? t.y : 0.0;
+  }
+  if (active && i < LA)
+  {
+    tmx_lds_d* rb = buf + i * bs;
+#pragma unroll
+    for (int c = 0; c < W; c += 2)
+      if (c < wn)
+        *(tmx_lds_d2*)(rb + j0 + c) = tmx_d2{ val[c], val[c + 1] };
+    if (i == 0 && j0 == 0)
+      rb[Zst] = fast_rcp(val[0]);
+  }
+  TMX_SYNC();
+  int k0 = 0, par = 0;
+  for (; k0 + LA <= ns; k0 += LA, par ^= 1)
+  {
+    if (active)
+      gj_sep_group<W, LA, LA>(val, buf + par * LA * bs, buf + (par ^ 1) * LA * bs, Zst, wn, j0, i, k0, k0 + LA < ns);
+    TMX_SYNC();
+  }
+  if constexpr (LA > 1)
+  {
+    const int rem = ns - k0;  // (wave-uniform: the barriers stand in uniform control flow)
+    if (rem == 1)
+    {
+      if (active)
+        gj_sep_group<W, 1, LA>(val, buf + par * LA * bs, buf + (par ^ 1) * LA * bs, Zst, wn, j0, i, k0, false);
+    }
+    else if (LA > 2 && rem == 2)
+    {
+      if (active)
+        gj_sep_group<W, (LA > 2 ? 2 : 1), LA>(val, buf + par * LA * bs, buf + (par ^ 1) * LA * bs, Zst, wn, j0, i, k0, false);
+    }
+  }
+  if (active)
+  {
+#pragma unroll
+    for (int c = 0; c < W; ++c)
+      if (c < wn && j0 + c < ns)
+        Mr[c] = val[c];
+  }
+  TMX_SYNC();
+}
+
 // Preconditions: the fast-path predicate of qp_solve_block and DevProblem::factor_fast; w.rho / w.sigma set.  In: the scaled problem.
 // Out: G, Zs, fac, dinv (and hr, Sinv) as kkt_factor(mode 0) + kkt_invert(partitioned) + admm_cache_weights leave them.
 TMX_DEVFN void factor_fast(const QpWs& w, const DevProblem* P, double delta, int tid, [[maybe_unused]] long long* pc, [[maybe_unused]] long long& tlast)
@@ -189,6 +373,7 @@ TMX_DEVFN void factor_fast(const QpWs& w, const DevProblem* P, double delta, int
   tmx_lds_d* const G = TMX_LDS_PTR(w.G);
   tmx_lds_d* const Zs = TMX_LDS_PTR(w.Zs);
   tmx_lds_d* const po = TMX_LDS_PTR(w.po);
+  tmx_lds_d* const sx = TMX_LDS_PTR(w.sx);
 #undef TMX_LDS_PTR
   DPart p;
   dpart_make(T, p);
@@ -262,7 +447,18 @@ TMX_DEVFN void factor_fast(const QpWs& w, const DevProblem* P, double delta, int
   }
   TMX_SYNC();
   TMX_FACTOR_TICK(3);
-  // 4. its dense inverse: lane = row, wave = column quarter (gj_rows; scratch: the separator exchange vectors)
+  // 4. its dense inverse: lane = row, wave = column quarter, three elimination steps per barrier (gj_sep_rows; scratch: the separator
+  //    exchange vectors w.sx, 6 x 64 doubles: room for three steps up to Zst = 56, the 7 x 30 problem's; a wider system keeps gj_rows).
+  //    DevProblem::dbg_flags bit 6 keeps gj_rows, one step per barrier, on every problem: same bits
+  constexpr int SEP_LA = 3;
+  if (TMX_UNI_B(!(P->dbg_flags & 64) && gj_sep_buf_doubles(Zst, SEP_LA) <= 6 * 64))
+  {
+    if (Zst <= 32)
+      gj_sep_rows<8, SEP_LA>(Zs, sx, Zst, ns, tid);
+    else
+      gj_sep_rows<16, SEP_LA>(Zs, sx, Zst, ns, tid);
+  }
+  else
   {
     const int i = tid & 63, seg = (tid >> 6) & 3;
     const bool active = i < ns && tid < 256;

@@ -157,7 +157,9 @@ struct DevProblem
   // bit 3 = the generic SQP shell around the QP solve (qp_structure) on a problem the specialised one can take (step_fast below);
   // bit 4 = the hashes of P by the loop over its columns and the generic exact evaluation and model values (evaluate_terms,
   //         sqp_model_values) on a problem that qualifies for the table and the merged evaluation (eval_fast below);
-  // bit 5 = the generic ADMM factorisation (kkt_invert: dpart_factor) on a problem of the dense fast path (factor_fast below)
+  // bit 5 = the generic ADMM factorisation (kkt_invert: dpart_factor) on a problem of the dense fast path (factor_fast below);
+  // bit 6 = the per-step forms inside factor_fast: gj_rows, one elimination step per barrier, for the separator inverse
+  //         (tests/test_factor_lookahead.py compares the three)
   int dbg_flags;
   // TotalTime terms ON THE BLOCK CHAIN (tmx_problem_upload: the only reason for the dense engine are these terms and the QP is over
   // its size limit, or TMX_TOTAL_TIME_CHAIN=1): tt_chain = n_tt (<= TMX_TT_MAX) and qp_dense = 0 - the structured QP kernels carry

@@ -122,7 +122,10 @@ typedef enum
      trajectory_costs.cpp:502-754, acc = x[i] - 2 x[i+1] + x[i+2] - target_j for i in [first_step, last_step - 2]:
      JointAccEqCost (squared cost, zero tolerances), JointAccIneqCost (two hinge rows per step and joint), JointAccEqConstraint,
      JointAccIneqConstraint.  Rows touch THREE consecutive waypoints and the squared cost couples waypoints i and i + 2: the QP
-     is no longer block tridiagonal, such problems are solved by the dense batched engine.                     */
+     is no longer block tridiagonal.  Costs and rows run on the banded block factorisation of the structured solver at any size;
+     next to rows on two waypoints with dense coupling blocks (LVS / cast collision, CartVel) the squared costs do above the dense
+     batched engine's size limit and the rows with the upload hook TMX_BAND_ROW_PAIR_CHAIN=1, and the dense batched engine takes
+     what is left (next to function costs or time-parameterised terms) - DESIGN.md 2.6, 2.6.1.                              */
   TMX_TERM_JOINT_ACC_EQ_COST = 13,
   TMX_TERM_JOINT_ACC_INEQ_COST = 14,
   TMX_TERM_JOINT_ACC_EQ_CNT = 15,

@@ -1,7 +1,7 @@
 """Phase profile (needs a -DTMX_PROFILE build: make -C trajopt_amd/csrc EXTRA=-DTMX_PROFILE).
    python tools/prof_phases.py [B] [full|first] [lib.so] [config[s]]   - first QP solve only (default) or the whole optimize() run
    ("full"); config 1 (default), 2, 3 or 4, or a problem of tests/test_band_pair_chain.py ("H", "H-nocost": without its smoothing
-   costs); the word "fine5" anywhere among the arguments names the slots of a -DTMX_PROFILE -DTMX_FINE=5 build"""
+   costs) or of tests/test_band_row_pair_chain.py ("P2", "P1": uploaded with TMX_BAND_ROW_PAIR_CHAIN=1); the word "fine5" anywhere among the arguments names the slots of a -DTMX_PROFILE -DTMX_FINE=5 build"""
 import sys, os, ctypes as C, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -29,7 +29,11 @@ if bp_name is not None:
     from trajopt_amd.problem import JointAccTermInfo, JointJerkTermInfo
     for k in (bp.SWITCH, "TMX_DENSE_QP_MAX_N"):
         os.environ.pop(k, None)
-    pci, x0 = bp.ALL[bp_name.split("-")[0]](B)
+    import test_band_row_pair_chain as br  # ("P1", "P2", ...: acceleration / jerk ROWS next to pair rows)
+    os.environ.pop(br.SWITCH, None)
+    if bp_name.split("-")[0] in br.ALL:
+        os.environ[br.SWITCH] = "1"
+    pci, x0 = (br.ALL if bp_name.split("-")[0] in br.ALL else bp.ALL)[bp_name.split("-")[0]](B)
     if bp_name.endswith("-nocost"):
         pci.cost_infos = [ti for ti in pci.cost_infos if not isinstance(ti, (JointAccTermInfo, JointJerkTermInfo))]
     desc = pci.to_desc()

@@ -6,8 +6,12 @@
                                                                                        dense-coupling chain with segmented sweeps) on another build
     python tools/time_band_pair_chain.py --crossover --batch 64                        first Model::optimize() on both QP engines
 
---problem is a problem of tests/test_band_pair_chain.py (E .. K, S1 .. S5); --no-cost drops its acceleration / jerk costs; --switch
-sets TMX_BAND_PAIR_CHAIN for the upload.  --crossover takes the 4-DOF test arm with the cast collision cost (pc.cfg(17)) plus the
+    python tools/time_band_pair_chain.py --problem P2 --batch 256                      acceleration / jerk ROWS next to such rows
+                                                                                       (profiles/band_row_pair_chain_timing.txt)
+
+--problem is a problem of tests/test_band_pair_chain.py (E .. K, S1 .. S5) or of tests/test_band_row_pair_chain.py (P1 .. P3, R1 .. R5:
+uploaded with TMX_BAND_ROW_PAIR_CHAIN=1; P2 / P1 are H / E with acceleration limits on top); --no-cost drops its squared
+acceleration / jerk costs; --switch sets TMX_BAND_PAIR_CHAIN for the upload.  --crossover takes the 4-DOF test arm with the cast collision cost (pc.cfg(17)) plus the
 acceleration cost at the largest number of waypoints whose QP stays within the dense engine's 448 variables.
 Prints one line per measurement: batch time per SQP run, QP solves, ADMM iterations, batch time per ADMM iteration."""
 import argparse
@@ -23,15 +27,18 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import parity_checks as pc  # noqa: E402
 import test_band_pair_chain as bp  # noqa: E402
+import test_band_row_pair_chain as br  # noqa: E402
 from trajopt_amd import abi, runtime  # noqa: E402
 from trajopt_amd.problem import JointAccTermInfo, JointJerkTermInfo  # noqa: E402
 
 
-def upload(pci, x0, lib, sw):
-    for k in (bp.SWITCH, "TMX_DENSE_QP_MAX_N"):  # (an override of the dense engine's limit would change what "switch unset" measures)
+def upload(pci, x0, lib, sw, rows=False):
+    for k in (bp.SWITCH, br.SWITCH, "TMX_DENSE_QP_MAX_N"):  # (an override of the dense engine's limit would change what "switch unset" measures)
         os.environ.pop(k, None)
     if sw is not None:
         os.environ[bp.SWITCH] = sw
+    if rows:
+        os.environ[br.SWITCH] = "1"
     ctx = runtime.Context(0, lib)
     ctx.upload(pci.to_desc(), abi.default_sqp_params(), abi.default_osqp_settings())
     ctx.set_x0(x0)
@@ -39,7 +46,7 @@ def upload(pci, x0, lib, sw):
 
 
 def whole_runs(args, pci, x0):
-    ctx = upload(pci, x0, args.lib, args.switch)
+    ctx = upload(pci, x0, args.lib, args.switch, rows=args.problem in br.ALL)
     times = []
     for rep in range(args.reps):
         ctx.set_x0(x0)
@@ -49,6 +56,8 @@ def whole_runs(args, pci, x0):
     r, c = ctx.results(), ctx.counters()
     best, B = min(times), x0.shape[0]
     route = ctx.band_pairs() if hasattr(ctx.lib, "tmx_debug_band_pairs") else False
+    if args.problem in br.ALL:
+        assert ctx.band_row_pairs()
     print(f"problem {args.problem}{' without the smoothing costs' if args.no_cost else ''} T={pci.basic_info.n_steps} B={B} switch={args.switch} "
           f"lib={args.lib or 'default'} n_max={ctx.n_max} R={ctx.R} banded route {int(route)} workspace {ctx.workspace_info()}: "
           f"runs {[round(t, 4) for t in times]} s, best {best:.4f} s, {best / B * 1e3:.3f} ms per SQP run (batch time / B), QP solves {c['n_qp_solves']}, "
@@ -91,7 +100,7 @@ def crossover(args):
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--problem", default="H", choices=sorted(bp.ALL))
+    ap.add_argument("--problem", default="H", choices=sorted(bp.ALL) + sorted(br.ALL))
     ap.add_argument("--batch", type=int, required=True)
     ap.add_argument("--no-cost", action="store_true")
     ap.add_argument("--switch", default=None, choices=("0", "1"))
@@ -101,7 +110,7 @@ def main():
     args = ap.parse_args()
     if args.crossover:
         return crossover(args)
-    pci, x0 = bp.ALL[args.problem](args.batch)
+    pci, x0 = (br.ALL if args.problem in br.ALL else bp.ALL)[args.problem](args.batch)
     if args.no_cost:
         pci.cost_infos = [ti for ti in pci.cost_infos if not isinstance(ti, (JointAccTermInfo, JointJerkTermInfo))]
     whole_runs(args, pci, x0)

@@ -149,7 +149,7 @@ STEP_LOG_HEAD = 16   # TMX_STEP_LOG_HEAD (include/tmx.h, tmx_sqp_step_log)
 
 # debug hooks outside include/tmx.h (tmx_debug_<name>(ctx) -> int: the upload's verdict on the engine of the QP solves, -1 without a
 # problem): (argtypes, restype); runtime.Context.debug_flag
-DEBUG_HOOKS = {name: ([C.c_void_p], C.c_int) for name in ("qp_dense", "tt_chain", "tv_chain", "band_pairs")}
+DEBUG_HOOKS = {name: ([C.c_void_p], C.c_int) for name in ("qp_dense", "tt_chain", "tv_chain", "band_pairs", "band_row_pairs")}
 
 
 class SqpParams(C.Structure):

@@ -1482,6 +1482,7 @@ static EngineChoice choose_engine(const Lowered& L, const DevProblem& P, const U
   // LVS / cast collision rows, no CartVel rows) all the blocks they add to the reduced KKT matrix are diagonal, and the problem runs
   // on the banded structured path at any size (band = max of the orders of costs and rows; DevProblem::band_rows).  Next to general
   // pair rows (dense coupling blocks) or to function costs (dynamic P) they keep the dense engine.
+  std::string br_why;  // with TMX_BAND_ROW_PAIR_CHAIN=1: what keeps them on the dense engine next to general pair rows
   if (L.stencil_rows)
   {
     int other_pairs = 0;
@@ -1495,7 +1496,40 @@ static EngineChoice choose_engine(const Lowered& L, const DevProblem& P, const U
       band = std::max(band, L.max_row_order);
     }
     else
-      qp_dense = true;
+    {
+      // ... next to general pair rows the first coupling block of the reduced KKT matrix is dense (Cd: the pair rows' w_r coef_r c2_r'
+      // plus, on its diagonal, the difference rows' first-coupling terms) and the far couplings stay diagonal (bk2 / bk3): the banded
+      // factorisation with a dense first coupling of DevProblem::band_pairs, with the far entries of the rows in the ADMM loop of
+      // band_rows - both flags.  OPT-IN, TMX_BAND_ROW_PAIR_CHAIN=1 (at any size); unset or "0" the dense engine and its limit, as
+      // before.  Squared acceleration / jerk costs of the same problem ride along (po2 / po3 enter bk2 / bk3).  Next to function costs,
+      // to time-parameterised terms or in the trajopt_sqp flavour the dense engine stays.
+      const bool able = TMX_LINK_ROWS && !qp_dense && other_pairs > 0 && P.D <= 255 && !L.tt_terms && !L.tv_terms && !P.use_time && !L.dyn_p &&
+                        P.flavor == TMX_FLAVOR_SCO;
+      if (able && hooks.band_row_pair_chain == '1')
+      {
+        E.band_rows = true;
+        E.band_pairs = true;
+        st_terms = true;
+        band = std::max(band, L.max_row_order);
+      }
+      else
+      {
+        if (hooks.band_row_pair_chain == '1')  // (the text of the refusal is the one of before unless the route was asked for)
+        {
+          if (L.dyn_p)
+            br_why = "function costs";
+          else if (L.tt_terms || L.tv_terms || P.use_time)
+            br_why = "time-parameterised terms";
+          else if (P.flavor != TMX_FLAVOR_SCO)
+            br_why = "the trajopt_sqp flavour";
+          else if (other_pairs == 0)
+            br_why = "more than 255 variables per waypoint";
+          else
+            br_why = "a build without rows on two waypoints";
+        }
+        qp_dense = true;
+      }
+    }
   }
   // squared acceleration / jerk costs alone keep the structured solver (banded block factorisation of the generic path).  Together
   // with general pair rows (LVS / cast collision rows, CartVel rows: dense coupling blocks) small problems keep the dense engine, bit
@@ -1546,7 +1580,8 @@ static EngineChoice choose_engine(const Lowered& L, const DevProblem& P, const U
     if (!L.tv_owner.empty())
       reason("squared joint-velocity costs with time" + tv_why);
     if (L.stencil_rows)
-      reason("acceleration / jerk rows next to collision / CartVel rows on two waypoints or to time-parameterised terms");
+      reason("acceleration / jerk rows next to collision / CartVel rows on two waypoints or to time-parameterised terms" +
+             (br_why.empty() ? std::string() : " (TMX_BAND_ROW_PAIR_CHAIN=1 does not apply: " + br_why + ")"));
     if (L.tt_terms && (int)L.tt_owner.size() > TMX_TT_MAX)
       reason("more than " + std::to_string(TMX_TT_MAX) + " TotalTime terms");
     else if (L.tt_terms && (band != 0 || L.dyn_p))
@@ -4160,6 +4195,14 @@ __attribute__((visibility("default"))) int tmx_debug_band_pairs(tmx_ctx* ctx)
   if (!ctx || !ctx->have_problem)
     return -1;
   return ctx->hp.band_pairs;
+}
+
+// ... and both band_rows and band_pairs (acceleration / jerk ROWS next to general pair rows on that factorisation, TMX_BAND_ROW_PAIR_CHAIN=1)
+__attribute__((visibility("default"))) int tmx_debug_band_row_pairs(tmx_ctx* ctx)
+{
+  if (!ctx || !ctx->have_problem)
+    return -1;
+  return (ctx->hp.band_rows && ctx->hp.band_pairs) ? 1 : 0;
 }
 
 // debug hook (not in include/tmx.h): 1 = fused persistent optimize() kernel (default), 0 = one launch chain per step

@@ -1253,11 +1253,32 @@ TMX_DEVFN void kkt_factor(const QpWs& w, const DevProblem* P, int mode, double s
       ws_bk3(w)[v] = b3;
     }
   // dense coupling blocks C_t = diag(po_t) + sum over the pair rows of waypoint t of  w_r coef_r c2_r'
-  if (w.n_link > 0 && !w.band_rows)
+  // Difference rows of order 2 / 3 NEXT TO general pair rows (band_rows and band_cd both): the sum over the rows at home waypoint t
+  // takes in the difference rows' w_r a_0 a_1 (coef and c2 of such a row are zero off its joint: a diagonal entry), and the diagonal
+  // entry (j, j) also gets the first-coupling terms of the difference rows of joint j at home waypoints t - 2 (w_r a_2 a_3) and t - 1
+  // (w_r a_1 a_2), a_2 / a_3 = ws_cf.  ORDER OF THE SUM of one entry, one thread per entry: po_t, then the rows at home waypoint
+  // t - 2, t - 1, t (ascending), inside a waypoint in list order - the same on the host build, the SIMT emulation and the device, and
+  // without difference rows the sum of before.  bk2 / bk3 are the loop above; bk1 is not read on this route.
+  if (w.n_link > 0 && (!w.band_rows || w.band_cd))
     for (int e = tid; e < (T - 1) * DD; e += NT)
     {
       const int t = e / DD, i = (e % DD) / D, j = e % D;
       double c = (i == j) ? w.po[t * D + i] : ((w.tvo != 0 && j == D - 1) ? ws_tvc(w)[t * D + i] : 0.0);  // (last column: P(x[t][i], tau[t + 1]))
+      if (w.band_rows && i == j)
+        for (int m = 2; m >= 1; --m)
+          if (m <= t)
+            for (int q = w.wl_start[t - m]; q < w.wl_start[t - m + 1]; ++q)
+            {
+              const int r = w.wl_list[q];
+              const int ci = w.c2i[r];
+              if (!w.act[r] || ci < 0)
+                continue;
+              const int f = ws_fo(w)[ci];
+              if (f == 0 || (f & 0xff) != j || (f >> 8) < m + 1)
+                continue;
+              const double am = (m == 1) ? w.c2[ci * D + j] : ws_cf(w)[2 * ci];
+              c += w.hr[r] * am * ws_cf(w)[2 * ci + (m - 1)];
+            }
       for (int q = w.wl_start[t]; q < w.wl_start[t + 1]; ++q)
       {
         const int r = w.wl_list[q];
@@ -1314,6 +1335,8 @@ TMX_DEVFN void kkt_factor(const QpWs& w, const DevProblem* P, int mode, double s
         double as = 0.0;
         if (tc == t)
           as = w.Sinv[t * DDS + j * DS + jc];
+        else if (w.band_cd && abs(tc - t) == 1)  // (dense first coupling: row = variable of the earlier waypoint)
+          as = tc > t ? w.Cd[(size_t)t * D * D + j * D + jc] : w.Cd[(size_t)tc * D * D + jc * D + j];
         else if (jc == j && abs(tc - t) <= 3)
         {
           const int lo = tc < t ? c : v, k = abs(tc - t);
@@ -1546,6 +1569,15 @@ TMX_DEVFN double band_col_norm(const QpWs& w, int v)
 // W_1[t]; later steps read Cd_s, s > t, and nothing behind the factorisation reads Cd (kkt_factor rebuilds all of it before the next
 // one).  An HBM workspace keeps Cd in HBM and has Mf | Nb | yb among its chain arrays in LDS (qp_ws_chain_to_lds): the factors of a
 // band-2 problem go there; those of a band-3 problem (3 T D^2) stay in the band slice in HBM.
+// band_rows AND band_pairs (difference rows of order 2 / 3 next to general pair rows): both of the above at once - the region
+// bk | cf | fo | dd sits behind the factors' and the M blocks' place in the band slice whether or not W moved out of it, and W overlays
+// Cd | Mf | Nb as described.  Two phases read Cd.  ADMM phase (polish_dd = 0): band_factor_impl<CD> as above - step t reads Cd_t
+// into M_1[t] (band slice) before a barrier and writes W_1[t] after it, on the doubles of Cd_t exactly (both are block t of
+// D^2-strided arrays from the same base); steps s > t read Cd_s, which no W_1[t'], t' <= t, covers, and W_2 / W_3 lie in the
+// Mf / Nb regions, never on Cd.  Polish (polish_dd = 1): kkt_factor rebuilds ALL of Cd over the dead W_1 of the ADMM phase,
+// band_factor_dd_impl<CD> reads it and writes only the double-double workspace in the band slice, band_solve_dd reads that
+// workspace only: W (fp64) is neither written nor read in the polish, so Cd is whole for every step.  The vector between the sweeps
+// (yb) is disjoint from Cd in both placements.
 TMX_DEVFN void qp_ws_attach_band(QpWs& w, int band, double* slice, int band_rows = 0, bool band_pairs = false)
 {
   w.band = band;
@@ -1872,7 +1904,10 @@ TMX_DEVFN BandDd band_dd_of(double* base, int D, int T)
   return b;
 }
 // as band_factor_impl: in K_tt in w.Sinv (fp64) and the couplings; out S_t^-1, W in double-double (dd)
-TMX_DEVFN void band_factor_dd_impl(const BandWs& w, double* ddbase, int tid, int NT)
+// CD (difference rows of order 2 / 3 next to general pair rows): M_1[t] starts from the transpose of the dense block Cd_t, read from
+// where kkt_factor wrote it - this routine writes the double-double workspace only, so Cd stays whole through the polish.
+template <bool CD = false>
+TMX_DEVFN void band_factor_dd_impl(const BandWs& w, double* ddbase, int tid, int NT, [[maybe_unused]] const double* Cd = nullptr)
 {
   const int D = w.D, DD = D * D, DS = w.DS, DDS = w.DDS, T = w.T, nb = w.band;
   const BandDd d = band_dd_of(ddbase, D, T);
@@ -1926,7 +1961,7 @@ TMX_DEVFN void band_factor_dd_impl(const BandWs& w, double* ddbase, int tid, int
         for (int e = tid; e < DD; e += NT)
         {
           const int i = e / D, c = e % D;
-          tdd val = dd_of((i == c) ? band_coupling(w, jj, t, i) : 0.0);
+          tdd val = dd_of((CD && jj == 1) ? Cd[(size_t)t * DD + c * D + i] : ((i == c) ? band_coupling(w, jj, t, i) : 0.0));
           for (int k = 1; jj + k <= nb && k <= t; ++k)
           {
             const tdd* A = d.M + ((size_t)(jj + k - 1) * T + (t - k)) * DD;
@@ -2168,10 +2203,17 @@ __device__ __attribute__((noinline)) static void band_solve_nl(BandWs w)
 }
 __device__ __attribute__((noinline)) static void band_factor_dd_nl(BandWs b, double* ddbase) { band_factor_dd_impl(b, ddbase, threadIdx.x, blockDim.x); }
 __device__ __attribute__((noinline)) static void band_solve_dd_nl(BandWs b, double* ddbase) { band_solve_dd_impl(b, ddbase, threadIdx.x, blockDim.x); }
+// (out of line like the others - the note above struct BandWs; called by the piecewise QP kernels only)
+__device__ __attribute__((noinline)) static void band_factor_dd_cd_nl(BandWs b, double* ddbase, const double* Cd)
+{
+  band_factor_dd_impl<true>(b, ddbase, threadIdx.x, blockDim.x, Cd);
+}
 TMX_DEVFN void band_factor(const QpWs& w, int, int)
 {
 #if TMX_LINK_ROWS
-  if (w.band_cd)  // (never with polish_dd: that is the polish of problems with difference rows)
+  if (w.polish_dd && w.band_cd)  // polish of problems with difference rows of order 2 / 3 next to general pair rows
+    band_factor_dd_cd_nl(band_ws_of(w), ws_dd(w), w.Cd);
+  else if (w.band_cd)
     band_factor_cd_nl(band_ws_of(w), w.Cd);
   else
 #endif
@@ -2191,7 +2233,9 @@ TMX_DEVFN void band_solve(const QpWs& w, int, int)
 TMX_DEVFN void band_factor(const QpWs& w, int tid, int NT)
 {
 #if TMX_LINK_ROWS
-  if (w.band_cd)
+  if (w.polish_dd && w.band_cd)
+    band_factor_dd_impl<true>(band_ws_of(w), ws_dd(w), tid, NT, w.Cd);
+  else if (w.band_cd)
     band_factor_impl<true>(band_ws_of(w), tid, NT, w.Cd);
   else
 #endif

@@ -199,6 +199,9 @@ struct DevProblem
   // engine's size limit, or with TMX_BAND_PAIR_CHAIN=1 (tmx_problem_upload): band_pairs = 1, band = 2 | 3 kept and qp_dense = 0 - the
   // piecewise QP kernels factor the block-banded reduced KKT matrix with a DENSE first coupling (QpWs::Cd, rebuilt by kkt_factor) and
   // the diagonal far couplings po2 / po3 (band_factor, tmx_qp.h).  0 everywhere else.  (Last, in the padding behind eval_fast.)
+  // With band_rows = 1 as well (TMX_BAND_ROW_PAIR_CHAIN=1): acceleration / jerk ROWS next to general pair rows - Cd also carries the
+  // difference rows' first-coupling terms on its diagonal, the far couplings are bk2 / bk3 (QpWs::bk), the polish runs the same
+  // factorisation in double-double.
   int band_pairs;
   // factor_fast: the ADMM factorisation of the dense fast path with the interior inverses inside one wave (tmx_factor.h) can take the
   // problem - the conditions of setup_fast, and the interior sub-matrices of a wave fit its 64 lanes (factor_fast_fits).  dbg_flags

@@ -54,6 +54,7 @@ struct EngineChoice
 {
   bool qp_dense = false, tt_chain = false, tv_chain = false, band_rows = false, st = false;
   bool band_pairs = false;  // squared acceleration / jerk costs next to general pair rows on the banded factorisation with a dense first coupling
+                            // (together with band_rows: acceleration / jerk ROWS next to general pair rows, TMX_BAND_ROW_PAIR_CHAIN=1)
   int band = 0;
   int R2 = 0;  // Lowered::R2, or 1 for squared velocity-with-time costs on the chain without a pair row (an unused second-block slot)
   std::string dense_reasons;  // what put the problem on the dense engine, comma-joined (text of the refusal above its size limit)
@@ -63,7 +64,7 @@ struct EngineChoice
 struct UploadHooks
 {
   // first character of the variable ('\0': unset)
-  char total_time_chain, vel_time_chain, band_pair_chain, force_coef_far, force_compact, row_perm, wave, tt_place;
+  char total_time_chain, vel_time_chain, band_pair_chain, band_row_pair_chain, force_coef_far, force_compact, row_perm, wave, tt_place;
   int dense_qp_max_n;  // size limit of the dense QP engine (QP variables incl. penalty variables); TMX_DENSE_QP_MAX_N lifts it for callers who accept the time
   bool verbose;
   static UploadHooks read()
@@ -76,6 +77,7 @@ struct UploadHooks
     h.total_time_chain = first("TMX_TOTAL_TIME_CHAIN");
     h.vel_time_chain = first("TMX_VEL_TIME_CHAIN");
     h.band_pair_chain = first("TMX_BAND_PAIR_CHAIN");
+    h.band_row_pair_chain = first("TMX_BAND_ROW_PAIR_CHAIN");
     h.force_coef_far = first("TMX_FORCE_COEF_FAR");
     h.force_compact = first("TMX_FORCE_COMPACT");
     h.row_perm = first("TMX_ROW_PERM");

@@ -225,6 +225,11 @@ class Context:
         with a dense first coupling (DevProblem::band_pairs, tmx_debug_band_pairs)"""
         return self.debug_flag("band_pairs") == 1
 
+    def band_row_pairs(self) -> bool:
+        """acceleration / jerk ROWS next to rows on two waypoints with dense coupling blocks run on the banded factorisation with a
+        dense first coupling (TMX_BAND_ROW_PAIR_CHAIN=1: DevProblem::band_rows and band_pairs both, tmx_debug_band_row_pairs)"""
+        return self.debug_flag("band_row_pairs") == 1
+
     def workspace_in_hbm(self) -> bool:
         return self.workspace_info()["in_hbm"]
 

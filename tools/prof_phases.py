@@ -1,13 +1,14 @@
 """Phase profile (needs a -DTMX_PROFILE build: make -C trajopt_amd/csrc EXTRA=-DTMX_PROFILE).
    python tools/prof_phases.py [B] [full|first] [lib.so] [config[s]]   - first QP solve only (default) or the whole optimize() run
    ("full"); config 1 (default), 2, 3 or 4, or a problem of tests/test_band_pair_chain.py ("H", "H-nocost": without its smoothing
-   costs) or of tests/test_band_row_pair_chain.py ("P2", "P1": uploaded with TMX_BAND_ROW_PAIR_CHAIN=1); the word "fine5" anywhere among the arguments names the slots of a -DTMX_PROFILE -DTMX_FINE=5 build"""
+   costs) or of tests/test_band_row_pair_chain.py ("P2", "P1": uploaded with TMX_BAND_ROW_PAIR_CHAIN=1); the word "fine5" anywhere among the arguments names the slots of a -DTMX_PROFILE -DTMX_FINE=5 build, the word "fine2" those of a -DTMX_FINE=2 build"""
 import sys, os, ctypes as C, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from trajopt_amd import configs, abi, runtime
 fine5 = "fine5" in sys.argv[1:]  # (a word, not a position: taken out before the positional arguments are read)
-sys.argv = [a for a in sys.argv if a != "fine5"]
+fine2 = "fine2" in sys.argv[1:]
+sys.argv = [a for a in sys.argv if a not in ("fine5", "fine2")]
 # a problem of tests/test_band_pair_chain.py in place of the configuration: "H", "F", ... (squared acceleration / jerk costs next to
 # pair rows); "H-nocost" drops the smoothing costs (the same rows on the segmented dense-coupling chain)
 bp_name = sys.argv[4] if len(sys.argv) > 4 and not sys.argv[4][0].isdigit() else None
@@ -66,6 +67,12 @@ if fine5:
     #  only its own phase "f:G inverses")
     names[13], names[14] = "f:assemble + eval+update: exact evaluation (eval_fast: + model values)", "f:G inverses + eval+update: model values"
     names[15], names[6] = "f:Schur+Zs + qp_structure: prefix counts + column pointers", "residuals+rho + qp_structure: hashing walks of A"
+# -DTMX_PROFILE -DTMX_FINE=2 builds (the word "fine2" anywhere among the arguments): the in-register check of the epoch-resident burst split
+# over reused slots - they keep their own phases too, so subtract the rows of a plain -DTMX_PROFILE run of the same commit.  Slot 9
+# keeps the re-zeroing and the decision of every check (and the store at the burst's end), slot 4 is free on the fast path.
+if fine2:
+    names[13], names[14], names[15] = "f:assemble + check: publish", "f:G inverses + check: reciprocals + 14 norms", "f:Schur+Zs + check: certificates"
+    names[6], names[4], names[9] = "residuals+rho + check: reduction", "burst: reload of the matrix rows", "check: re-zeroing + decision, burst exit"
 out = list(out)
 # Slot 5 is a phase TIME only on the generic path ("phase C").  On the dense fast path (config 1 without smoothing costs) the
 # epoch-resident burst uses it as a COUNTER (tmx_part.h: pc[5] += 1 + (go_on << 20) per in-register check): decode it and keep it

@@ -4101,7 +4101,8 @@ __attribute__((visibility("default"))) tmx_status tmx_debug_admm_iters(tmx_ctx* 
 // diagonal KKT blocks instead of the MFMA one, bit 1 = generic QP setup, bit 2 = generic polish on the dense fast path, bit 3 = generic
 // SQP shell around the QP solve (qp_structure) on a problem the specialised one can take, bit 4 = the hashes of P by the loop over its
 // columns and the generic exact evaluation and model values on a problem of eval_fast, bit 5 = the generic ADMM factorisation on a
-// problem of factor_fast, bit 6 = one elimination step per barrier in the separator inverse of factor_fast
+// problem of factor_fast, bit 6 = one elimination step per barrier in the separator inverse of factor_fast, bit 7 = no in-register
+// filter in the epoch-resident ADMM burst: qp_check_nl at every check, on norms it forms itself
 __attribute__((visibility("default"))) tmx_status tmx_debug_set_flags(tmx_ctx* ctx, int flags)
 {
   if (!ctx || !ctx->have_problem || !ctx->dp)
@@ -4138,6 +4139,18 @@ __attribute__((visibility("default"))) int tmx_debug_factor_fast(tmx_ctx* ctx)
   if (!ctx || !ctx->have_problem)
     return -1;
   return ctx->hp.factor_fast;
+}
+
+// debug hook (not in include/tmx.h): the row lists of the uploaded problem by waypoint (DevProblem::wp_start, T + 1 entries) into out[0 .. cap);
+// returns T + 1, or -1 without a problem or with too small a buffer (tests/test_burst_check.py: the list lengths mod 4 its shapes cover)
+__attribute__((visibility("default"))) int tmx_debug_wp_start(tmx_ctx* ctx, int* out, int cap)
+{
+  if (!ctx || !ctx->have_problem || !ctx->hp.wp_start || !out || cap < ctx->hp.T + 1)
+    return -1;
+  if (hipSetDevice(ctx->device) != hipSuccess ||
+      hipMemcpy(out, ctx->hp.wp_start, sizeof(int) * (size_t)(ctx->hp.T + 1), hipMemcpyDeviceToHost) != hipSuccess)
+    return -1;
+  return ctx->hp.T + 1;
 }
 
 // debug hook (not in include/tmx.h): 1 when the uploaded problem qualifies for the specialised SQP shell around the QP solve

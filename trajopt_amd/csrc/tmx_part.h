@@ -1568,7 +1568,9 @@ TMX_DEVFN int admm_burst_core(const QpWs& w, const DevProblem* P, int n_iter, bo
   // cache are still in registers, so the 14 norms of the termination test cost two exchanges (y of the rows grouped by waypoint
   // as e was; x with 8 slots per waypoint) and one block reduction instead of a sweep over index lists in LDS.  Every per-element
   // value is formed with the operations and in the order of compute_residuals / at_rows / p_times (products and sums, no FMA;
-  // four partial sums over the waypoint's row list, remainder into the first): same bits.
+  // four partial sums over the waypoint's row list, remainder into the first): same bits.  The A'y sum of norms14 decides per GROUP
+  // of four list entries, not per entry, where a product goes; what it adds beyond at_rows' own terms are products with a cached
+  // coefficient +0.0, that is +-0.0, to sums that are never -0.0 - the argument stands at the sum.
   auto publish_xy = [&]() __attribute__((always_inline)) {
 #pragma unroll
     for (int q = 0; q < NR; ++q)
@@ -1582,8 +1584,43 @@ TMX_DEVFN int admm_burst_core(const QpWs& w, const DevProblem* P, int n_iter, bo
   // per-row regions, recomputed by certs8.  Formed here ONCE per check, all loads first and the Newton steps of all of them stage by
   // stage (lock-step), then read from registers.  Same function on the same operands: same bits.
   double rc_er[NR], rc_eba[NR][NAX], rc_da[NR][NAX], rc_pv[2];
+  // ---- the operands of one check.  Temporaries: written by check_far_loads / check_rcps, read by norms14 and certs8 of the SAME check
+  // (certs8 used to load every one of them again through the generic pointers of QpWs), dead at the reduction - nothing of this lives
+  // across the iterations.  x_po: the couplings po[v - D], po[v] of p_times under its guards vt > 0, vt < T - 1.  A wave with interior
+  // variables holds them for the whole burst (cprev = po[v - D] exactly when v >= D, which is vt > 0, and 0 else; cnext = po[v]; both
+  // constant during a solve and used under the unchanged guards, so a product is formed with the same operand as before); the other
+  // waves do not keep them across the loop and read them once per check with a typed LDS load.
+  double x_er[NR], x_eba[NR][NAX], x_da[NR][NAX], x_pv[2], x_pd = 0.0, x_po[2] = { 0.0, 0.0 };
+  // Da is the only array of the check in the far (always-HBM) region of the workspace, and constant during a solve.  Its loads are
+  // requested here, ONCE per check and typed as global loads (a flat load also counts on lgkmcnt and would be waited for at the next
+  // barrier): the epoch mode calls this in front of the barrier that precedes publish_xy, so that the latency lies under the two
+  // barriers and the publish instead of stalling the wave four times inside the check.  (As compiled today the one-slack
+  // instantiations carry every request across the barriers; the two-slack ones wait for the first request of a row before they
+  // issue the second, which then stays in flight - profiles/r14/r14_prof_phases_table.txt.)
+  auto check_far_loads = [&]() __attribute__((always_inline)) {
+#if TMX_IS_GCN
+    typedef __attribute__((address_space(1))) const double glb_cd;
+    glb_cd* Da = (glb_cd*)w.Da;
+#else
+    const double* Da = w.Da;
+#endif
+#pragma unroll
+    for (int q = 0; q < NR; ++q)
+    {
+      // unconditional loads at clamped indices (one offset per row, then the requests): written as `oka ? Da[a] : 1.0`
+      // every entry was a branch around its own offset load, wait and request - four LDS round trips in front of the barrier
+      const bool ok = g[q].act;
+      const int a0 = w.aoff[ok ? rowi[q] : 0];
+#pragma unroll
+      for (int k = 0; k < NAX; ++k)
+      {
+        const bool oka = ok && k < g[q].na;
+        const double t = Da[oka ? a0 + k : 0];
+        x_da[q][k] = oka ? t : 1.0;
+      }
+    }
+  };
   auto check_rcps = [&]() __attribute__((always_inline)) {
-    double x_er[NR], x_eba[NR][NAX], x_da[NR][NAX], x_pv[2];
 #pragma unroll
     for (int q = 0; q < NR; ++q)
     {
@@ -1596,11 +1633,21 @@ TMX_DEVFN int admm_burst_core(const QpWs& w, const DevProblem* P, int n_iter, bo
         const bool oka = ok && k < g[q].na;
         const int a = oka ? w.aoff[r] + k : 0;
         x_eba[q][k] = oka ? w.Eba[a] : 1.0;
-        x_da[q][k] = oka ? w.Da[a] : 1.0;
       }
     }
     x_pv[0] = pv ? w.Ebp[v] : 1.0;
     x_pv[1] = pv ? w.Dp[v] : 1.0;
+    x_pd = pv ? w.pd[v] : 0.0;
+    if constexpr (INTW)
+    {
+      x_po[0] = cprev;
+      x_po[1] = cnext;
+    }
+    else
+    {
+      x_po[0] = (pv && vt > 0) ? h.po[v - D] : 0.0;
+      x_po[1] = pv ? h.po[v] : 0.0;
+    }
 #if TMX_IS_GCN
     // fast_rcp, stage by stage over all operands
     double e_er[NR], e_eba[NR][NAX], e_da[NR][NAX], e_pv[2];
@@ -1723,42 +1770,58 @@ TMX_DEVFN int admm_burst_core(const QpWs& w, const DevProblem* P, int n_iter, bo
         m[5] = fmax(m[5], fabs(einv * ax));
       }
       // (P x)_v: p_times
-      double px = w.pd[v] * xp;
+      double px = x_pd * xp;
       if (vt > 0)
-        px = px + w.po[v - D] * h.tp[vp - 8];
+        px = px + x_po[0] * h.tp[vp - 8];
       if (vt < w.T - 1)
-        px = px + w.po[v] * h.tp[vp + 8];
+        px = px + x_po[1] * h.tp[vp + 8];
       // (A' y)_v: at_rows over the waypoint's row list (n entries): groups of four into four partial sums, remainder into the first
       const int n = q_end > 0 ? q_end - q0v : 0, n4 = n & ~3;
       double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
       {
+        // Group gi holds entries 4 gi .. 4 gi + 3; ng = n / 4 groups are full.  ONE lane-varying predicate per group instead of one or
+        // two per entry:
+        //  * gi < ng (full): entry k goes to partial sum k & 3, as at_rows does;
+        //  * gi == ng (the remainder): its entries below n go to s0 in list order, after every full group of s0 - at_rows' order;
+        //    its entries from n on, and every entry of the groups behind it, are products of a cached coefficient that is +0.0 (cj / cjx
+        //    beyond the list) and a finite slot of the grouped buffer (zero-filled at burst entry, then y of other rows): +-0.0.
+        //    A partial sum starts at +0.0 and a sum of IEEE doubles is -0.0 only if both operands are, so none ever is -0.0, and
+        //    adding +-0.0 to it leaves every bit as it is: those entries may be added anywhere, and are added to s0 with the rest.
+        // The predicates come from a value the compiler cannot see through: known to be burst-invariant, they were hoisted in front
+        // of the iteration loop as SGPR pairs, spilled to VGPR lanes there and read back lane by lane in every check.
+        int ng = n >> 2;
+#if TMX_IS_GCN
+        asm volatile("" : "+v"(ng));
+#endif
         const tmx_lds_d2* ep = reinterpret_cast<const tmx_lds_d2*>(h.hr + e0off);
+        constexpr int NE = 16 + 2 * CJX;  // cached entries
+        double pe[NE + 2];
   #pragma unroll
         for (int k2 = 0; k2 < 8 + CJX; ++k2)
         {
           const tmx_d2 e2 = ep[k2];
-          const double p0 = cjv(2 * k2) * e2.x, p1 = cjv(2 * k2 + 1) * e2.y;
-          // entries 2 k2 and 2 k2 + 1: partial sum (k & 3) inside the groups of four, the first one in the remainder
-          const int ka = 2 * k2, kb = 2 * k2 + 1;
-          if ((ka & 3) == 0)
+          pe[2 * k2] = cjv(2 * k2) * e2.x;
+          pe[2 * k2 + 1] = cjv(2 * k2 + 1) * e2.y;
+        }
+  #pragma unroll
+        for (int gi = 0; gi < (NE + 3) / 4; ++gi)
+        {
+          const bool rem = gi >= ng;
+          const double a0 = s0 + pe[4 * gi];
+          double r = a0;
+          if (4 * gi + 1 < NE)
           {
-            s0 = (ka < n) ? s0 + p0 : s0;
-            if (kb < n4)
-              s1 = s1 + p1;
-            else if (kb < n)
-              s0 = s0 + p1;
+            r = r + pe[4 * gi + 1];
+            s1 = rem ? s1 : s1 + pe[4 * gi + 1];
           }
-          else
+          if (4 * gi + 2 < NE)
           {
-            if (ka < n4)
-              s2 = s2 + p0;
-            else if (ka < n)
-              s0 = s0 + p0;
-            if (kb < n4)
-              s3 = s3 + p1;
-            else if (kb < n)
-              s0 = s0 + p1;
+            r = r + pe[4 * gi + 2];
+            s2 = rem ? s2 : s2 + pe[4 * gi + 2];
           }
+          if (4 * gi + 3 < NE)
+            s3 = rem ? s3 : s3 + pe[4 * gi + 3];  // (entry 4 ng + 3 is never below n)
+          s0 = rem ? r : a0;
         }
       }
       for (int q = q_rest; q < q_end; ++q)
@@ -1833,26 +1896,25 @@ TMX_DEVFN int admm_burst_core(const QpWs& w, const DevProblem* P, int n_iter, bo
       const RowRegsT<NAX>& gq = g[q];
       if (gq.act)
       {
-        const int r = rowi[q];
+        // (Er, Eba, Da of this row: the operands check_rcps / check_far_loads read under the same guards)
         const double dy = kp_dyr[q];
-        m[14] = fmax(m[14], fabs(w.Er[r] * dy));
+        m[14] = fmax(m[14], fabs(x_er[q] * dy));
 #pragma unroll
         for (int k = 0; k < NAX; ++k)
           if (k < gq.na)
           {
-            const int a = w.aoff[r] + k;
             const double da = kp_dya[q][k];
-            m[14] = fmax(m[14], fabs(w.Eba[a] * da));
+            m[14] = fmax(m[14], fabs(x_eba[q][k] * da));
             const double dinv = rc_da[q][k];
             m[15] = fmax(m[15], fabs((gq.sa[k] * dy + gq.bb[k] * da) * dinv));
-            m[16] = fmax(m[16], fabs(w.Da[a] * kd_dxa[q][k]));
+            m[16] = fmax(m[16], fabs(x_da[q][k] * kd_dxa[q][k]));
           }
       }
     }
     if (pv)
     {
       const double dy = kp_dyb;
-      m[14] = fmax(m[14], fabs(w.Ebp[v] * dy));
+      m[14] = fmax(m[14], fabs(x_pv[0] * dy));
       // (A' dy)_v over the waypoint's row list from the grouped buffer (any summation order: the result is only compared with
       // a threshold it must exceed twofold)
       double s0 = 0.0, s1 = 0.0;
@@ -1870,12 +1932,12 @@ TMX_DEVFN int admm_burst_core(const QpWs& w, const DevProblem* P, int n_iter, bo
         s0 += w.coef[w.wp_list[q] * D + vj] * h.sx[e0off + (q - q0v)];
       const double dinv = rc_pv[1];
       m[15] = fmax(m[15], fabs(((s0 + s1) + bb * dy) * dinv));
-      m[16] = fmax(m[16], fabs(w.Dp[v] * kd_dxp));
-      double px = w.pd[v] * kd_dxp;
+      m[16] = fmax(m[16], fabs(x_pv[1] * kd_dxp));
+      double px = x_pd * kd_dxp;
       if (vt > 0)
-        px += w.po[v - D] * h.ty[vp - 8];
+        px += x_po[0] * h.ty[vp - 8];
       if (vt < w.T - 1)
-        px += w.po[v] * h.ty[vp + 8];
+        px += x_po[1] * h.ty[vp + 8];
       m[17] = fmax(m[17], fabs(px * dinv));
     }
   };
@@ -1910,6 +1972,7 @@ TMX_DEVFN int admm_burst_core(const QpWs& w, const DevProblem* P, int n_iter, bo
 #pragma unroll
       for (int k = 0; k < 22; ++k)
         m[k] = 0.0;
+      check_far_loads();
       check_rcps();
       norms14(m);
       double m14[14];
@@ -1942,6 +2005,9 @@ TMX_DEVFN int admm_burst_core(const QpWs& w, const DevProblem* P, int n_iter, bo
       next = min(next, (iter_done / rint + 1) * rint);
     const int n = next - iter_done;
     load_matrix_rows();
+#if defined(TMX_FINE) && TMX_FINE == 2  // (slot 4 is free on this path: the reload by itself; slot 9 keeps the re-zeroing and the decision)
+    TMX_TICK(4);
+#endif
     TMX_RETIRE_FLAT();
     for (int it = 0; it < n - 1; ++it)
       iteration(TmxTag<false>{});
@@ -1949,6 +2015,7 @@ TMX_DEVFN int admm_burst_core(const QpWs& w, const DevProblem* P, int n_iter, bo
       iteration(TmxTag<true>{});
     iter_done = next;
     TMX_TICK(2);
+    check_far_loads();  // requested here, waited for in check_rcps behind the two barriers
     TMX_SYNC();  // every thread is past phase C of the last iteration: tp / hr / sx / ty are free
     publish_xy();
     if (certs_ok)
@@ -2029,6 +2096,9 @@ TMX_DEVFN int admm_burst_core(const QpWs& w, const DevProblem* P, int n_iter, bo
       if ((rho_new > rho0 * rtol) || (rho_new < rho0 / rtol))
         go_on = false;
     }
+    // DevProblem::dbg_flags bit 7: the filter never continues - qp_check_nl, the authority, runs at every check (on norms it forms itself:
+    // tmx_solve.h); tests/test_burst_check.py compares the two in one library
+    go_on = go_on && !(P->dbg_flags & 128);
     go_on = __builtin_amdgcn_readfirstlane(go_on ? 1 : 0) != 0;
     TMX_TICK(9);
 #if defined(TMX_PROFILE) && !(defined(TMX_PROFILE_LOOP) && TMX_PROFILE_LOOP == 2)

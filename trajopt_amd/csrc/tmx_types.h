@@ -159,7 +159,10 @@ struct DevProblem
   //         sqp_model_values) on a problem that qualifies for the table and the merged evaluation (eval_fast below);
   // bit 5 = the generic ADMM factorisation (kkt_invert: dpart_factor) on a problem of the dense fast path (factor_fast below);
   // bit 6 = the per-step forms inside factor_fast: gj_rows, one elimination step per barrier, for the separator inverse
-  //         (tests/test_factor_lookahead.py compares the three)
+  //         (tests/test_factor_lookahead.py compares the three);
+  // bit 7 = the in-register residual check of the epoch-resident ADMM burst (admm_burst_core, tmx_part.h) never continues and
+  //         qp_check_nl ignores the norms the burst left: the authority runs at every check on norms of the generic compute_residuals
+  //         (tests/test_burst_check.py compares the two)
   int dbg_flags;
   // TotalTime terms ON THE BLOCK CHAIN (tmx_problem_upload: the only reason for the dense engine are these terms and the QP is over
   // its size limit, or TMX_TOTAL_TIME_CHAIN=1): tt_chain = n_tt (<= TMX_TT_MAX) and qp_dense = 0 - the structured QP kernels carry

@@ -683,6 +683,35 @@ TMX_API tmx_status tmx_check_trajectories(tmx_ctx* ctx, const tmx_check_config* 
 TMX_API tmx_status tmx_best_trajectories_checked(tmx_ctx* ctx, const tmx_check_config* cfg, int64_t* best_index /* Q */,
                                                  double* best_cost /* Q */, double* best_min_distance /* Q, optional */,
                                                  double* x_out /* Q x T x D, optional */);
+/* ---- Self-collision in the check: tesseract's contact manager tests every active link against everything, filtered by the
+ *      allowed-collision matrix, so checkTrajectory reports an arm folded onto itself as "in collision".  Here the caller lists the
+ *      link pairs that ARE tested (the positive form of an allowed-collision matrix; there is no implicit "adjacent links are
+ *      allowed"); the collision TERMS do not know them.  link_pairs[n_pairs][2], indices as tmx_link_sphere::link, kept in the
+ *      caller's order; n_pairs == 0 (or NULL) clears them, and so does a new tmx_problem_upload.  The host expands the list into
+ *      primitive pairs p = (sa, sb): link pair, then sa, then sb, all ascending; a pair whose link carries no primitive is legal and
+ *      contributes nothing.  TMX_ERR_INVALID for a == b, an index outside 0 .. n_dof-1, a pair given twice in either order or
+ *      n_pairs < 0; TMX_ERR_STATE without an uploaded problem or while a launch is pending.                                       */
+TMX_API tmx_status tmx_check_set_link_pairs(tmx_ctx* ctx, const int32_t* link_pairs /* n_pairs x 2 */, int32_t n_pairs);
+/* the number of link pairs set and of the primitive pairs they expand to (either pointer optional) */
+TMX_API tmx_status tmx_check_link_pairs(tmx_ctx* ctx, int32_t* n_pairs, int32_t* n_primitive_pairs);
+/* the closest self-contact of a trajectory (ties: the lowest (step, substate, primitive pair)); all integers -1 and 1e300 without one */
+typedef struct
+{
+  double min_distance;
+  int32_t step, primitive_a, primitive_b, substate;
+} tmx_check_self_worst;
+/* tmx_check_trajectories with the contacts (step t, sub-state or swept sub-segment i, primitive pair p) in the place of (t, i, s, o):
+ * the same per-step layout, sub-state rule, meaning of entry T-1, x_host == NULL, use_time, flavours, multi-query batches and errors
+ * (the cast refusal for capsule links included).  Distance of a pair: types 0 / 1 / 2 - both primitives at the frames of the same
+ * sub-state, the cores a point (sphere) or a segment (capsule), d = |pa - pb| - ra - rb at the closest points of the cores; types
+ * 3 / 4 - each primitive swept between sub-states i and i+1 of its own link (a swept sphere is a segment core, a swept hull the
+ * convex hull of both placements: BOTH sides are swept, the conservative test); with a hull on a side the distance is GJK / EPA on
+ * the two convex sets.  penetration = sum max(0, margin - d) in ascending (i, p) order.  Without pairs, or with zero primitive
+ * pairs, every entry is 1e300 / 0 / -1.  With pairs set, tmx_best_trajectories_checked counts a seed as free iff its obstacle minima
+ * AND its self minima are all >= margin, and best_min_distance is the smaller of the two.                                        */
+TMX_API tmx_status tmx_check_self_trajectories(tmx_ctx* ctx, const tmx_check_config* cfg, const double* x_host, int32_t n,
+                                               double* min_distance /* n x T, optional */, double* penetration /* n x T, optional */,
+                                               tmx_check_self_worst* worst /* n, optional */);
 /* ... or let the library own its communicator: rank 0 calls tmx_nccl_unique_id and ships the 128 bytes to the other ranks by
  * any means (bench.py: torch.distributed broadcast); every rank then calls tmx_nccl_init (ncclCommInitRank on the context's
  * device and stream).  The communicator is destroyed with the context.                                           */

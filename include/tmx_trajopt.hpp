@@ -1544,6 +1544,7 @@ public:
     const tmx_sqp_params p = param_.toTmx();
     check(tmx_problem_upload(ctx_, &prob_->desc(), &p, &osqp_));
     uploaded_ = true;
+    sendSelfPairs();  // (an upload clears them)
     if (n_queries_ > 1)  // (before tmx_batch_set_x0: it runs the first exact evaluation)
     {
       check(tmx_queries_set(ctx_, n_queries_));
@@ -1670,6 +1671,7 @@ public:
       const tmx_sqp_params p = param_.toTmx();
       check(tmx_problem_upload(ctx_, &prob_->desc(), &p, &osqp_));
       uploaded_ = true;
+      sendSelfPairs();
     }
     const std::size_t n = trajs.empty() ? static_cast<std::size_t>(batch_) : trajs.size();
     std::vector<double> md(n * T), pen(n * T);
@@ -1687,8 +1689,81 @@ public:
     }
     return out;
   }
+  /** Self-collision in the check (tmx_check_set_link_pairs): the pairs of moving links that checkSelfTrajectories tests and that
+      bestPerQuery(cfg) counts next to the obstacles - the positive form of tesseract's allowed-collision matrix; nothing is implied
+      for adjacent links.  By link name (JointGroup::link_names, or the tip link; an unknown name throws) or by link index (the
+      child link of joint k, as tmx_link_sphere::link).  The pairs are kept here and sent again after every upload of this class's
+      own (an upload clears the library's); an empty list clears them.  What the library refuses (a link paired with itself, a
+      pair given twice, an index outside the chain) throws here when the problem is uploaded already, else at the upload. */
+  void setSelfCollisionPairs(const std::vector<std::pair<std::string, std::string>>& link_names)
+  {
+    std::vector<std::pair<int, int>> idx;
+    for (const auto& pr : link_names)
+    {
+      const int a = prob_->GetKin()->linkIndex(pr.first), b = prob_->GetKin()->linkIndex(pr.second);
+      if (a < 0 || b < 0)
+        printAndThrow("setSelfCollisionPairs: unknown link name: " + (a < 0 ? pr.first : pr.second));
+      idx.emplace_back(a, b);
+    }
+    setSelfCollisionPairs(idx);
+  }
+  void setSelfCollisionPairs(const std::vector<std::pair<int, int>>& links)
+  {
+    std::vector<int32_t> flat;
+    for (const auto& pr : links)
+    {
+      flat.push_back(static_cast<int32_t>(pr.first));
+      flat.push_back(static_cast<int32_t>(pr.second));
+    }
+    if (uploaded_)
+      check(tmx_check_set_link_pairs(ctx_, flat.empty() ? nullptr : flat.data(), static_cast<int32_t>(flat.size() / 2)));
+    self_pairs_ = flat;
+  }
+  /** checkTrajectories for the link pairs of setSelfCollisionPairs (tmx_check_self_trajectories): the same layout, the closest
+      contact names the two primitives */
+  struct SelfTrajectoryCheck
+  {
+    std::vector<DblVec> min_distance, penetration;  // [n][n_steps]
+    std::vector<tmx_check_self_worst> worst;        // [n]
+    std::vector<bool> free;                         // every min_distance >= margin
+  };
+  SelfTrajectoryCheck checkSelfTrajectories(const CollisionCheckConfig& cfg, const std::vector<DblVec>& trajs = {})
+  {
+    const std::size_t nv = numVars(), T = static_cast<std::size_t>(prob_->GetNumSteps());
+    const tmx_check_config c = cfg.toTmx();
+    std::vector<double> x;
+    for (const DblVec& t : trajs)
+    {
+      if (t.size() != nv)
+        printAndThrow("checkSelfTrajectories: trajectory has wrong length. expected " + std::to_string(nv) + " got " + std::to_string(t.size()));
+      x.insert(x.end(), t.begin(), t.end());
+    }
+    if (!trajs.empty() && !uploaded_)
+    {
+      const tmx_sqp_params p = param_.toTmx();
+      check(tmx_problem_upload(ctx_, &prob_->desc(), &p, &osqp_));
+      uploaded_ = true;
+      sendSelfPairs();
+    }
+    const std::size_t n = trajs.empty() ? static_cast<std::size_t>(batch_) : trajs.size();
+    std::vector<double> md(n * T), pen(n * T);
+    SelfTrajectoryCheck out;
+    out.worst.resize(n);
+    check(tmx_check_self_trajectories(ctx_, &c, trajs.empty() ? nullptr : x.data(), static_cast<int32_t>(n), md.data(), pen.data(), out.worst.data()));
+    for (std::size_t b = 0; b < n; ++b)
+    {
+      out.min_distance.emplace_back(md.begin() + static_cast<std::ptrdiff_t>(b * T), md.begin() + static_cast<std::ptrdiff_t>((b + 1) * T));
+      out.penetration.emplace_back(pen.begin() + static_cast<std::ptrdiff_t>(b * T), pen.begin() + static_cast<std::ptrdiff_t>((b + 1) * T));
+      bool fr = true;
+      for (double d : out.min_distance.back())
+        fr = fr && d >= cfg.margin;
+      out.free.push_back(fr);
+    }
+    return out;
+  }
   /** the best COLLISION-FREE converged seed of every query under cfg after optimize() (tmx_best_trajectories_checked; works with one
-      query): QueryBest, and the winner's clearance (1e300: none) */
+      query): QueryBest, and the winner's clearance (1e300: none).  With setSelfCollisionPairs a seed is free iff it clears the
+      obstacles AND itself, and the clearance is the smaller of the two. */
   struct QueryBestChecked : QueryBest
   {
     DblVec min_distance;
@@ -1815,6 +1890,11 @@ private:
       check(tmx_sqp_run(ctx_, 1, nullptr));
     }
   }
+  void sendSelfPairs()
+  {
+    if (!self_pairs_.empty())
+      check(tmx_check_set_link_pairs(ctx_, self_pairs_.data(), static_cast<int32_t>(self_pairs_.size() / 2)));
+  }
   std::size_t numVars() const { return static_cast<std::size_t>(prob_->GetNumSteps()) * static_cast<std::size_t>(prob_->GetNumVarsPerStep()); }
   void check(tmx_status s)
   {
@@ -1836,6 +1916,7 @@ private:
   std::vector<double> seeds_;
   int32_t batch_{ 0 };
   bool uploaded_{ false };  // tmx_problem_upload has run (optimize(), or checkTrajectories before it)
+  std::vector<int32_t> self_pairs_;  // setSelfCollisionPairs: link index pairs, sent again after every upload
   OptResults results_;
   std::vector<OptResults> batch_results_;
   std::size_t best_{ 0 };

@@ -11,6 +11,12 @@ profiles/check_trajectories_timing.txt:
 Every way runs REPS times after one warm-up; medians and spreads (max - min) in ms.
 
     python tools/time_check.py [--reps 5] [--out profiles/check_trajectories_timing.txt]
+
+With --self the self-collision side instead (tmx_check_set_link_pairs with every pair of NON-ADJACENT links that carry primitives), written
+to profiles/check_self_timing.txt: tmx_check_self_trajectories next to tmx_check_trajectories on the same resident batch, and
+tmx_best_trajectories_checked on 32 queries x 32 seeds with and without the pairs.
+
+    python tools/time_check.py --self [--reps 5] [--out profiles/check_self_timing.txt]
 """
 import argparse
 import os
@@ -53,12 +59,66 @@ def item_count(x, n_dof, cfg, so):
     return sub, sub * so
 
 
+def main_self(args):
+    pci, start, goal = configs.config1()
+    B, T, D = Q * S, pci.basic_info.n_steps, pci.robot.n_dof
+    links = sorted({ls[0] for ls in pci.robot.link_spheres})
+    pairs = [(a, b) for a in links for b in links if b - a >= 2]
+    sqp, osqp = abi.default_sqp_params(), abi.default_osqp_settings()
+    cfg = abi.default_check_config()
+    ctx = runtime.Context(0, args.lib)
+    ctx.upload(pci.to_desc(), sqp, osqp)
+    ctx.check_set_link_pairs(pairs)
+    n_pairs, pp = ctx.check_link_pairs()
+    so = len(pci.robot.link_spheres) * len(pci.obstacles)
+    lines = ["glass_upright: %d trajectories x %d waypoints, %d link spheres x %d obstacle(s), %d non-adjacent link pairs = %d primitive pairs; "
+             "LVS_CONTINUOUS, margin %g, lvs %g, max_substates %d; one MI355X, %d runs after one warm-up" %
+             (B, T, len(pci.robot.link_spheres), len(pci.obstacles), n_pairs, pp, cfg.margin, cfg.longest_valid_segment_length, cfg.max_substates, args.reps),
+             "way                                                          ms (median, spread)   swept sub-segments        items"]
+    ctx.set_x0(configs.seeds_for(1, pci, start, goal, B))
+    ctx.run(0)
+    res = ctx.results()
+    sub, items = item_count(res["x"], D, cfg, so)
+    med, spread = timed(lambda: ctx.check_trajectories(cfg), args.reps)
+    lines.append("%-60s %9.3f  %9.3f   %18d %12d" % ("tmx_check_trajectories, resident batch, 3 outputs", med, spread, sub, items))
+    sub, items = item_count(res["x"], D, cfg, pp)
+    med, spread = timed(lambda: ctx.check_self_trajectories(cfg), args.reps)
+    slf = ctx.check_self_trajectories(cfg)
+    lines.append("%-60s %9.3f  %9.3f   %18d %12d" % ("tmx_check_self_trajectories, the same batch, 3 outputs", med, spread, sub, items))
+    lines.append("    %d of %d trajectories free of themselves; smallest self distance %.6f" % (int(slf["free"].sum()), B, float(slf["min_distance"].min())))
+    goals = goals_for(pci, goal)
+    ctx.upload(pci.to_desc(), sqp, osqp)
+    ctx.set_queries(Q)
+    ctx.set_query_targets(pci.term_index(pci.cnt_infos[-1]), goals)
+    ctx.set_x0(np.concatenate([configs.seeds_for(1, pci, start, goals[q], S, first=q * S) for q in range(Q)]))
+    ctx.run(0)
+    conv = ctx.results()["status"] == abi.OPT_CONVERGED
+    med, spread = timed(lambda: ctx.best_trajectories_checked(cfg), args.reps)
+    plain = ctx.best_trajectories_checked(cfg)
+    lines.append("%-60s %9.3f  %9.3f" % ("tmx_best_trajectories_checked, %d x %d seeds, no pairs" % (Q, S), med, spread))
+    ctx.check_set_link_pairs(pairs)
+    med, spread = timed(lambda: ctx.best_trajectories_checked(cfg), args.reps)
+    both = ctx.best_trajectories_checked(cfg)
+    lines.append("%-60s %9.3f  %9.3f" % ("tmx_best_trajectories_checked, %d x %d seeds, with the pairs" % (Q, S), med, spread))
+    lines.append("    %d of %d seeds converged; queries with a free converged seed: %d without the pairs, %d with them" %
+                 (int(conv.sum()), B, int(plain["found"].sum()), int(both["found"].sum())))
+    ctx.close()
+    text = "\n".join(lines) + "\n"
+    print(text, end="")
+    with open(args.out or os.path.join(ROOT, "profiles", "check_self_timing.txt"), "w") as f:
+        f.write(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "check_trajectories_timing.txt"))
+    ap.add_argument("--out", default=None, help="default: profiles/check_trajectories_timing.txt (profiles/check_self_timing.txt with --self)")
     ap.add_argument("--lib", default=None, help="another build of the library (default: the product library)")
+    ap.add_argument("--self", dest="self_check", action="store_true", help="time the self-collision side instead")
     args = ap.parse_args()
+    if args.self_check:
+        return main_self(args)
+    args.out = args.out or os.path.join(ROOT, "profiles", "check_trajectories_timing.txt")
     pci, start, goal = configs.config1()
     B, T, D = Q * S, pci.basic_info.n_steps, pci.robot.n_dof
     so = len(pci.robot.link_spheres) * len(pci.obstacles)

@@ -252,6 +252,17 @@ class CheckWorst(C.Structure):
 CHECK_WORST_DTYPE = [("min_distance", "<f8"), ("step", "<i4"), ("primitive", "<i4"), ("obstacle", "<i4"), ("substate", "<i4")]
 
 
+class CheckSelfWorst(C.Structure):
+    """tmx_check_self_worst: the closest self-contact of a trajectory (all integers -1 without one)"""
+    _fields_ = [
+        ("min_distance", C.c_double),
+        ("step", C.c_int32), ("primitive_a", C.c_int32), ("primitive_b", C.c_int32), ("substate", C.c_int32),
+    ]
+
+
+CHECK_SELF_WORST_DTYPE = [("min_distance", "<f8"), ("step", "<i4"), ("primitive_a", "<i4"), ("primitive_b", "<i4"), ("substate", "<i4")]
+
+
 def default_check_config(evaluator_type: int = 4, margin: float = 0.0, longest_valid_segment_length: float = 0.05, max_substates: int = 32):
     """tmx_default_check_config: LVS_CONTINUOUS, margin 0, longest valid segment 0.05, at most 32 sub-states per segment"""
     c = CheckConfig()

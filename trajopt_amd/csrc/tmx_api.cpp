@@ -10,6 +10,7 @@
 
 #include "tmx_kernels.h"
 #include "tmx_check.h"
+#include "tmx_check_self.h"
 #include "tmx_wave_kernels.h"
 #include "tmx_wave_plan.h"
 #include "tmx_row_perm.h"
@@ -101,6 +102,10 @@ struct tmx_ctx
   // the last call used per QP (tmx_qp_engine_last)
   int qp_engine{ TMX_QP_ENGINE_DENSE };
   std::vector<int> qp_last_engine, qp_last_block, qp_last_nblocks, qp_last_place;
+  // Self-collision side of the trajectory check (tmx_check_set_link_pairs): the link pairs in the caller's order, the primitive pairs
+  // they expand to (host mirror and device table, 2 ints each), and the link of every primitive of the uploaded problem
+  std::vector<int> check_link_pairs, check_prim_pairs, h_ls_link;
+  int* d_check_pairs{ nullptr };
 };
 
 template <typename T>
@@ -261,6 +266,8 @@ void tmx_destroy(tmx_ctx* ctx)
     (void)hipFree(ctx->d_pair);
   if (ctx->d_best)
     (void)hipFree(ctx->d_best);
+  if (ctx->d_check_pairs)
+    (void)hipFree(ctx->d_check_pairs);
 #ifdef TMX_HOST_EMU
   delete ctx->h_tail;
 #else
@@ -1986,6 +1993,16 @@ static tmx_status configure_launch(tmx_ctx* ctx, const DevProblem& P, const Lowe
   return TMX_OK;
 }
 
+// no link pairs: the self-collision side of the check tests nothing
+static void drop_check_pairs(tmx_ctx* ctx)
+{
+  if (ctx->d_check_pairs)
+    (void)hipFree(ctx->d_check_pairs);
+  ctx->d_check_pairs = nullptr;
+  ctx->check_link_pairs.clear();
+  ctx->check_prim_pairs.clear();
+}
+
 // back to one query: the per-query tables go and the next batch carries null pointers (ensure_batch)
 static void drop_queries(tmx_ctx* ctx)
 {
@@ -2044,6 +2061,8 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
   ctx->Bcap = ctx->Balloc = 0;
   ctx->have_problem = false;
   drop_queries(ctx);  // a new problem has one query
+  drop_check_pairs(ctx);  // ... and no link pairs
+  ctx->h_ls_link.clear();
   DevProblem& P = ctx->hp;
   fill_basic_info(d, sqp, osqp, P);
   Lowered L;
@@ -2062,6 +2081,7 @@ tmx_status tmx_problem_upload(tmx_ctx* ctx, const tmx_problem_desc* d, const tmx
   for (int k = 0; k < d->n_terms; ++k)
     ctx->term_kind[(size_t)k] = d->terms[k].kind;
   ctx->n_dof = DK;
+  ctx->h_ls_link = L.ls_link;
   const EngineChoice E = choose_engine(L, P, hooks);
   P.band = E.band;
   P.band_rows = E.band_rows ? 1 : 0;
@@ -3754,7 +3774,8 @@ struct CheckPlan
   size_t smem;
   int nt;
 };
-static tmx_status check_plan(tmx_ctx* ctx, const tmx_check_config* cfg, int n, const char* who, CheckPlan& pl)
+// (items_per_substate < 0: the S x O pairs of the obstacle check; the self-collision check passes its primitive pairs)
+static tmx_status check_plan(tmx_ctx* ctx, const tmx_check_config* cfg, int n, const char* who, CheckPlan& pl, long long items_per_substate = -1)
 {
   const std::string w(who);
   if (!cfg)
@@ -3790,7 +3811,7 @@ static tmx_status check_plan(tmx_ctx* ctx, const tmx_check_config* cfg, int n, c
     return TMX_ERR_UNSUPPORTED;
   }
   const int DK = ctx->hp.DK, T = ctx->hp.T;
-  const long long SO = (long long)ctx->hp.S * ctx->hp.O;
+  const long long SO = items_per_substate < 0 ? (long long)ctx->hp.S * ctx->hp.O : items_per_substate;
   CheckArgs& a = pl.a;
   a.type = type;
   a.kmax = cfg->max_substates < 2 ? 2 : cfg->max_substates;
@@ -3909,6 +3930,173 @@ tmx_status tmx_check_trajectories(tmx_ctx* ctx, const tmx_check_config* cfg, con
   return TMX_OK;
 }
 
+// ---- self-collision side of the check (tmx_check_self.h) ----
+tmx_status tmx_check_set_link_pairs(tmx_ctx* ctx, const int32_t* link_pairs, int32_t n_pairs)
+{
+  if (!ctx)
+    return TMX_ERR_INVALID;
+  if (!ctx->have_problem)
+  {
+    ctx->err = "tmx_check_set_link_pairs: no problem uploaded (call tmx_problem_upload first; an upload clears the pairs)";
+    return TMX_ERR_STATE;
+  }
+  TMX_REFUSE_WHILE_PENDING(ctx);
+  if (n_pairs < 0)
+  {
+    ctx->err = "tmx_check_set_link_pairs: n_pairs must be >= 0 (0 clears the pairs)";
+    return TMX_ERR_INVALID;
+  }
+  if (!link_pairs)
+    n_pairs = 0;
+  const int DK = ctx->hp.DK;
+  for (int k = 0; k < n_pairs; ++k)
+  {
+    const int a = link_pairs[2 * k], b = link_pairs[2 * k + 1];
+    if (a < 0 || a >= DK || b < 0 || b >= DK)
+    {
+      ctx->err = "tmx_check_set_link_pairs: pair " + std::to_string(k) + " = (" + std::to_string(a) + ", " + std::to_string(b) +
+                 "): a link index must be in 0 .. n_dof - 1 = " + std::to_string(DK - 1);
+      return TMX_ERR_INVALID;
+    }
+    if (a == b)
+    {
+      ctx->err = "tmx_check_set_link_pairs: pair " + std::to_string(k) + " = (" + std::to_string(a) + ", " + std::to_string(b) +
+                 "): a link is not tested against itself";
+      return TMX_ERR_INVALID;
+    }
+    for (int j = 0; j < k; ++j)
+      if ((link_pairs[2 * j] == a && link_pairs[2 * j + 1] == b) || (link_pairs[2 * j] == b && link_pairs[2 * j + 1] == a))
+      {
+        ctx->err = "tmx_check_set_link_pairs: pair " + std::to_string(k) + " = (" + std::to_string(a) + ", " + std::to_string(b) +
+                   ") repeats pair " + std::to_string(j) + " (a pair is given once, in either order)";
+        return TMX_ERR_INVALID;
+      }
+  }
+  // primitive pairs: link pair, then sa, then sb, all ascending
+  std::vector<int> prim;
+  for (int k = 0; k < n_pairs; ++k)
+    for (size_t sa = 0; sa < ctx->h_ls_link.size(); ++sa)
+      if (ctx->h_ls_link[sa] == link_pairs[2 * k])
+        for (size_t sb = 0; sb < ctx->h_ls_link.size(); ++sb)
+          if (ctx->h_ls_link[sb] == link_pairs[2 * k + 1])
+          {
+            prim.push_back((int)sa);
+            prim.push_back((int)sb);
+          }
+  HIPCHK(hipSetDevice(ctx->device));
+  int* d_new = nullptr;
+  if (!prim.empty())
+  {
+    void* p = nullptr;
+    HIPCHK(hipMalloc(&p, prim.size() * sizeof(int)));
+    d_new = static_cast<int*>(p);
+    if (hipMemcpy(d_new, prim.data(), prim.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess)
+    {
+      (void)hipFree(d_new);
+      ctx->err = "tmx_check_set_link_pairs: the copy of the primitive-pair table failed";
+      return TMX_ERR_DEVICE;
+    }
+  }
+  drop_check_pairs(ctx);
+  ctx->d_check_pairs = d_new;
+  ctx->check_link_pairs.assign(link_pairs, link_pairs + 2 * (size_t)n_pairs);
+  ctx->check_prim_pairs = std::move(prim);
+  return TMX_OK;
+}
+
+tmx_status tmx_check_link_pairs(tmx_ctx* ctx, int32_t* n_pairs, int32_t* n_primitive_pairs)
+{
+  if (!ctx)
+    return TMX_ERR_INVALID;
+  if (n_pairs)
+    *n_pairs = (int32_t)(ctx->check_link_pairs.size() / 2);
+  if (n_primitive_pairs)
+    *n_primitive_pairs = (int32_t)(ctx->check_prim_pairs.size() / 2);
+  return TMX_OK;
+}
+
+static tmx_status check_self_launch(tmx_ctx* ctx, const CheckPlan& pl, const double* d_x, int n, double* d_min, double* d_pen, int* d_key)
+{
+  const int PP = (int)(ctx->check_prim_pairs.size() / 2);
+  if (ctx->hull)
+    TMX_LAUNCH(k_check_self_hull, n * pl.a.chunks, pl.nt, pl.smem, ctx->stream, ctx->dp, ctx->db, d_x, pl.a, ctx->d_check_pairs, PP, d_min, d_pen, d_key);
+  else
+    TMX_LAUNCH(k_check_self, n * pl.a.chunks, pl.nt, pl.smem, ctx->stream, ctx->dp, ctx->db, d_x, pl.a, ctx->d_check_pairs, PP, d_min, d_pen, d_key);
+  HIPCHK(hipGetLastError());
+  return TMX_OK;
+}
+
+tmx_status tmx_check_self_trajectories(tmx_ctx* ctx, const tmx_check_config* cfg, const double* x_host, int32_t n, double* min_distance,
+                                       double* penetration, tmx_check_self_worst* worst)
+{
+  if (!ctx)
+    return TMX_ERR_INVALID;
+  if (!ctx->have_problem)
+  {
+    ctx->err = "tmx_check_self_trajectories: no problem uploaded (call tmx_problem_upload first)";
+    return TMX_ERR_STATE;
+  }
+  TMX_REFUSE_WHILE_PENDING(ctx);
+  if (n < 1)
+  {
+    ctx->err = "tmx_check_self_trajectories: n must be >= 1";
+    return TMX_ERR_INVALID;
+  }
+  CheckPlan pl;
+  tmx_status rc;
+  if ((rc = check_plan(ctx, cfg, n, "tmx_check_self_trajectories", pl, (long long)(ctx->check_prim_pairs.size() / 2))) != TMX_OK)
+    return rc;
+  const size_t T = (size_t)ctx->hp.T, NX = (size_t)ctx->hp.NX;
+  if (!x_host)
+  {
+    if (ctx->Bcap == 0)
+    {
+      ctx->err = "tmx_check_self_trajectories: x_host == NULL checks the current iterates, but the context holds no batch (call tmx_batch_set_x0 first)";
+      return TMX_ERR_STATE;
+    }
+    if (n != ctx->hb.B)
+    {
+      ctx->err = "tmx_check_self_trajectories: with x_host == NULL n must equal the batch (" + std::to_string(ctx->hb.B) + ")";
+      return TMX_ERR_INVALID;
+    }
+  }
+  else
+    for (size_t i = 0; i < (size_t)n * NX; ++i)
+      if (!std::isfinite(x_host[i]))
+      {
+        ctx->err = "tmx_check_self_trajectories: non-finite trajectory value";
+        return TMX_ERR_INVALID;
+      }
+  HIPCHK(hipSetDevice(ctx->device));
+  struct PoolGuard
+  {
+    std::vector<void*> pool;
+    ~PoolGuard() { free_pool(pool); }
+  } guard;
+  double *d_x = nullptr, *d_min = nullptr, *d_pen = nullptr;
+  int* d_key = nullptr;
+  tmx_check_self_worst* d_worst = nullptr;
+  if ((x_host && (rc = dalloc(ctx, guard.pool, &d_x, (size_t)n * NX, false)) != TMX_OK) ||
+      (rc = dalloc(ctx, guard.pool, &d_min, (size_t)n * T, false)) != TMX_OK || (rc = dalloc(ctx, guard.pool, &d_pen, (size_t)n * T, false)) != TMX_OK ||
+      (rc = dalloc(ctx, guard.pool, &d_key, (size_t)n * T * 2, false)) != TMX_OK ||
+      (worst && (rc = dalloc(ctx, guard.pool, &d_worst, (size_t)n, false)) != TMX_OK))
+    return rc;
+  if (x_host)
+    HIPCHK(hipMemcpyAsync(d_x, x_host, sizeof(double) * (size_t)n * NX, hipMemcpyHostToDevice, ctx->stream));
+  if ((rc = check_self_launch(ctx, pl, x_host ? d_x : ctx->hb.x, n, d_min, d_pen, d_key)) != TMX_OK)
+    return rc;
+  if (worst)
+  {
+    TMX_LAUNCH(k_check_self_worst, (n + pl.nt - 1) / pl.nt, pl.nt, 0, ctx->stream, (int)n, (int)T, d_min, d_key, ctx->d_check_pairs, d_worst);
+    HIPCHK(hipGetLastError());
+  }
+  if ((rc = d2h(ctx, min_distance, d_min, (size_t)n * T)) != TMX_OK || (rc = d2h(ctx, penetration, d_pen, (size_t)n * T)) != TMX_OK ||
+      (rc = d2h(ctx, worst, d_worst, (size_t)n)) != TMX_OK)
+    return rc;
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return TMX_OK;
+}
+
 tmx_status tmx_best_trajectories_checked(tmx_ctx* ctx, const tmx_check_config* cfg, int64_t* best_index, double* best_cost,
                                          double* best_min_distance, double* x_out)
 {
@@ -3948,6 +4136,24 @@ tmx_status tmx_best_trajectories_checked(tmx_ctx* ctx, const tmx_check_config* c
   // one check launch (the per-step minima of the converged seeds stay on the device), one reduction launch, one copy
   if ((rc = check_launch(ctx, pl, ctx->hb.x, B, d_min, d_pen, d_key)) != TMX_OK)
     return rc;
+  if (!ctx->check_prim_pairs.empty())
+  {
+    // link pairs are set: the self minima of the converged seeds, folded into the obstacle minima (a minimum does not round) - the
+    // reduction below then sees "free of the obstacles and of itself" and the smaller clearance
+    CheckPlan ps;
+    if ((rc = check_plan(ctx, cfg, B, "tmx_best_trajectories_checked", ps, (long long)(ctx->check_prim_pairs.size() / 2))) != TMX_OK)
+      return rc;
+    ps.a.converged_only = 1;
+    double *d_smin = nullptr, *d_spen = nullptr;
+    int* d_skey = nullptr;
+    if ((rc = dalloc(ctx, guard.pool, &d_smin, (size_t)B * T, false)) != TMX_OK || (rc = dalloc(ctx, guard.pool, &d_spen, (size_t)B * T, false)) != TMX_OK ||
+        (rc = dalloc(ctx, guard.pool, &d_skey, (size_t)B * T * 2, false)) != TMX_OK)
+      return rc;
+    if ((rc = check_self_launch(ctx, ps, ctx->hb.x, B, d_smin, d_spen, d_skey)) != TMX_OK)
+      return rc;
+    TMX_LAUNCH(k_check_fold_min, (B * T + pl.nt - 1) / pl.nt, pl.nt, 0, ctx->stream, ctx->db, pl.a.converged_code, (int)B, (int)T, d_smin, d_min);
+    HIPCHK(hipGetLastError());
+  }
   TMX_LAUNCH(k_argmin_queries_checked, Q, pl.nt, 16 * sizeof(double) + 18 * sizeof(int), ctx->stream, ctx->db, pl.a.converged_code, S, NX, T,
              pl.a.margin, d_min, d_cost, d_idx, d_clear, d_x);
   HIPCHK(hipGetLastError());

@@ -64,6 +64,9 @@ _SIGS = {
     "tmx_default_check_config": ([C.POINTER(abi.CheckConfig)], None),
     "tmx_check_trajectories": ([C.c_void_p, C.POINTER(abi.CheckConfig), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
     "tmx_best_trajectories_checked": ([C.c_void_p, C.POINTER(abi.CheckConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+    "tmx_check_set_link_pairs": ([C.c_void_p, C.c_void_p, C.c_int32], C.c_int),
+    "tmx_check_link_pairs": ([C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)], C.c_int),
+    "tmx_check_self_trajectories": ([C.c_void_p, C.POINTER(abi.CheckConfig), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
 }
 ABI_SYMBOLS = tuple(_SIGS.keys())
 
@@ -417,9 +420,43 @@ class Context:
         self._chk(self.lib.tmx_check_trajectories(self.h, C.byref(cfg), _ptr(x), n, _ptr(md), _ptr(pen), _ptr(worst)))
         return dict(min_distance=md, penetration=pen, worst=worst, free=(md >= cfg.margin).all(axis=1))
 
+    def check_set_link_pairs(self, pairs=None):
+        """tmx_check_set_link_pairs: the link pairs [(a, b), ...] (indices as the link of a link sphere) that the self-collision check
+        tests, in this order; None or an empty list clears them, and so does upload()"""
+        p = np.ascontiguousarray(pairs if pairs is not None else [], dtype=np.int32).reshape(-1)
+        if p.size % 2:
+            raise TmxError(f"check_set_link_pairs: pairs must be [n][2], got {p.size} values")
+        self._chk(self.lib.tmx_check_set_link_pairs(self.h, _ptr(p) if p.size else None, p.size // 2))
+
+    def check_link_pairs(self):
+        """tmx_check_link_pairs: (link pairs set, primitive pairs they expand to)"""
+        n, npp = C.c_int32(), C.c_int32()
+        self._chk(self.lib.tmx_check_link_pairs(self.h, C.byref(n), C.byref(npp)))
+        return n.value, npp.value
+
+    def check_self_trajectories(self, cfg: abi.CheckConfig = None, x=None):
+        """tmx_check_self_trajectories: check_trajectories with the primitive pairs of check_set_link_pairs in the place of the
+        (primitive, obstacle) pairs: dict(min_distance [n][T], penetration [n][T], worst [n] (min_distance, step, primitive_a,
+        primitive_b, substate), free [n])"""
+        cfg = self.default_check_config() if cfg is None else cfg
+        if x is not None:
+            x = np.ascontiguousarray(x, dtype=np.float64)
+            if x.ndim == 2:
+                x = x[None]
+            if x.ndim != 3 or x.shape[1] != self.T or x.shape[2] != self.D:
+                raise TmxError(f"check_self_trajectories: x must be [n][{self.T}][{self.D}], got {list(x.shape)}")
+            n = x.shape[0]
+        else:
+            n = self.B
+        md, pen = np.zeros((n, self.T)), np.zeros((n, self.T))
+        worst = np.zeros(n, dtype=abi.CHECK_SELF_WORST_DTYPE)
+        self._chk(self.lib.tmx_check_self_trajectories(self.h, C.byref(cfg), _ptr(x), n, _ptr(md), _ptr(pen), _ptr(worst)))
+        return dict(min_distance=md, penetration=pen, worst=worst, free=(md >= cfg.margin).all(axis=1))
+
     def best_trajectories_checked(self, cfg: abi.CheckConfig = None):
         """tmx_best_trajectories_checked: the best COLLISION-FREE converged seed of every query under cfg: dict(index [Q] in the batch
-        (-1: none), total_cost [Q] (1e300: none), min_distance [Q] (the winner's clearance), x [Q][T][D] (zeros: none), found [Q])"""
+        (-1: none), total_cost [Q] (1e300: none), min_distance [Q] (the winner's clearance), x [Q][T][D] (zeros: none), found [Q]).
+        With link pairs set (check_set_link_pairs) free means free of the obstacles and of the robot itself"""
         cfg = self.default_check_config() if cfg is None else cfg
         bi, bc, md = np.zeros(self.Q, np.int64), np.zeros(self.Q), np.zeros(self.Q)
         x = np.zeros((self.Q, self.T, self.D))
@@ -449,6 +486,7 @@ class Context:
 
 class BatchedTrustRegionSQP:
     _queries_sent = False
+    _link_pairs = ()
     """sco::BasicTrustRegionSQP for a batch of seeds (optimizers.hpp:137-194): setParameters, initialize, optimize,
     results.  `prob` is a trajopt_amd.problem.ProblemConstructionInfo (the hatched-problem description)."""
 
@@ -490,6 +528,15 @@ class BatchedTrustRegionSQP:
             self.ctx.set_query_targets(self.pci.term_index(ti), np.stack(rows))
         self._queries_sent = True
 
+    def _ensure_uploaded(self):
+        if not self._uploaded:
+            self.desc = self.pci.to_desc()
+            self.ctx.upload(self.desc, self.params, self.osqp)
+            self._uploaded = True
+            self._queries_sent = False
+            if self._link_pairs:
+                self.ctx.check_set_link_pairs(self._link_pairs)
+
     def setParameters(self, params: abi.SqpParams):
         self.params = params
         self._uploaded = False
@@ -503,11 +550,7 @@ class BatchedTrustRegionSQP:
         T, D = self.pci.basic_info.n_steps, self.pci.robot.n_dof + (1 if self.pci.basic_info.use_time else 0)
         if x.ndim != 3 or x.shape[1] != T or x.shape[2] != D:
             raise TmxError(f"initialization vector has wrong length. expected [B,{T},{D}] got {list(x.shape)}")
-        if not self._uploaded:
-            self.desc = self.pci.to_desc()
-            self.ctx.upload(self.desc, self.params, self.osqp)
-            self._uploaded = True
-            self._queries_sent = False
+        self._ensure_uploaded()
         if self.queries is not None and not self._queries_sent:
             self._send_queries()     # (before set_x0: it runs the first exact evaluation)
         elif self.queries is None and self.ctx.Q != 1:
@@ -539,16 +582,30 @@ class BatchedTrustRegionSQP:
     def check_trajectories(self, cfg: abi.CheckConfig = None, x=None):
         """Context.check_trajectories on the optimizer's problem: x [n][T][D] (e.g. the initial trajectories, as the reference's tests
         check them before optimize()), or None for the current iterates of the batch.  Uploads the problem if that has not happened"""
-        if not self._uploaded:
-            self.desc = self.pci.to_desc()
-            self.ctx.upload(self.desc, self.params, self.osqp)
-            self._uploaded = True
-            self._queries_sent = False
+        self._ensure_uploaded()
         return self.ctx.check_trajectories(cfg, x)
+
+    def check_set_link_pairs(self, pairs=None):
+        """Context.check_set_link_pairs on the optimizer's problem: the link pairs of the self-collision check (None: none).  They are
+        kept here and sent again after every upload of the optimizer's own (an upload clears the context's pairs)"""
+        pairs = [] if pairs is None else [(int(a), int(b)) for a, b in pairs]
+        self._ensure_uploaded()
+        self.ctx.check_set_link_pairs(pairs)
+        self._link_pairs = pairs
+
+    def check_link_pairs(self):
+        self._ensure_uploaded()
+        return self.ctx.check_link_pairs()
+
+    def check_self_trajectories(self, cfg: abi.CheckConfig = None, x=None):
+        """Context.check_self_trajectories on the optimizer's problem, as check_trajectories"""
+        self._ensure_uploaded()
+        return self.ctx.check_self_trajectories(cfg, x)
 
     def best_per_query(self, check: abi.CheckConfig = None):
         """the best converged seed of every query: dict(index [Q] in the batch (-1: none converged), total_cost [Q], x [Q][T][D], found [Q]);
-        with a CheckConfig the best COLLISION-FREE converged seed under it, and min_distance [Q] = its clearance"""
+        with a CheckConfig the best COLLISION-FREE converged seed under it (free of the obstacles and, with check_set_link_pairs, of the
+        robot itself), and min_distance [Q] = its clearance"""
         if check is not None:
             return self.ctx.best_trajectories_checked(check)
         bi, bc = self.ctx.argmin_queries()
